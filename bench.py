@@ -323,6 +323,30 @@ def stats3(v):
     return {"min": v[0], "median": v[len(v) // 2], "max": v[-1]} if v else None
 
 
+DUMP_MAX_RECORDS = 1 << 20            # --dump-outputs: 32 MiB of records + 8 MiB of their indices (float64), under the 64 MB cap
+DUMP_SEED = 0x5EE9
+
+
+def dump_outputs(dirname, counts, rec):
+    """--dump-outputs DIR: what a caller of the timed path received from its last step, as float64 .npy files --
+    counts.npy (lines, matching lines, hits, records, headers) and, for the record workloads, records.npy [k, 4]
+    (line, start, end, dist) with record_index.npy [k], the positions of those rows in the full record list: all of
+    them up to DUMP_MAX_RECORDS, else a sorted sample of that many drawn with a fixed seed."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    keys = ("nlines", "nmatchlines", "nhits", "nrecords", "nheaders")
+    np.save(os.path.join(dirname, "counts.npy"), np.array([counts[k] for k in keys], dtype=np.float64))
+    if rec is None:
+        return
+    n = len(rec)
+    if n > DUMP_MAX_RECORDS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_RECORDS, replace=False))
+    else:
+        idx = np.arange(n)
+    np.save(os.path.join(dirname, "records.npy"), rec[idx].astype(np.float64))
+    np.save(os.path.join(dirname, "record_index.npy"), idx.astype(np.float64))
+
+
 def reference_full_check(text, n, read_len, pattern, tau, mode, rec, matching_lines, shard_lines=1_000_000):
     """EVERY line of the run against the reference itself (oracle/_ref/seeq_ref, the reference's own C files): the device text
     goes to /dev/shm in waves of P shards (P = the host cores this process may use), P pinned reference processes print
@@ -643,6 +667,8 @@ def bench_chrom(args):
     torch.cuda.synchronize()
     el = (time.perf_counter() - t0) / args.steps
     rec = sc.records(cnt["nrecords"])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cnt, rec)
     k = 64 << 20
     sample = torch.cat([text[L - k:L], text[2 * L - k:2 * L]]).contiguous()
     exp = Oracle().buffer_scan(pattern, tau, sample.cpu().numpy(), dev.SQ_ALL)
@@ -905,7 +931,7 @@ def run_workload(ctx, name, n, steps, warmup, candidates, first_steps, check_lin
                          "whole_step_frac": (n * L + 16 * local["nrecords"] + 8 * launches_per_step) / (own_elapsed / steps) / 1e9 / HBM_PEAK_GBS},
             "dtype": "int (u16 automaton state ids; exact-pass columns u32 bit-vectors)" if kern in ("k_stream", "k_pair") else "u32 bit-vectors",
         }
-    live = {"text": text, "tb": tb, "sc": sc, "pat": pat, "rec": rec, "local": local, "opt": opt, "want": want, "mode": mode,
+    live = {"text": text, "tb": tb, "sc": sc, "pat": pat, "rec": rec, "local": local, "total": total, "opt": opt, "want": want, "mode": mode,
             "PATTERN": PATTERN, "TAU": TAU, "READ_LEN": READ_LEN, "rec_cap": rec_cap, "stream": stream}
     if not keep:
         sc.close(); pat.close()
@@ -958,7 +984,12 @@ def main():
                          "reference binary's output, outside the timed region; sample: the oracle sample only")
     ap.add_argument("--check-lines", type=int, default=1_000_000,
                     help="prefix verified against the oracle (plus every 97th 64 Ki-line block and the segment seams); 0 = no check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (counts; records, or a seeded sample of at most "
+                         "%d of them) as float64 .npy files under DIR (rank 0)" % DUMP_MAX_RECORDS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.workload == "chrom":
         if args.gpus != 1:
@@ -1032,6 +1063,11 @@ def main():
     if args.dry_run:
         print(json.dumps(sec))
         return
+    if rank == 0 and args.dump_outputs:
+        rec = live["rec"]
+        if rec is None and live["want"] == dev.WANT_RECORDS:
+            rec = live["sc"].records(live["local"]["nrecords"])
+        dump_outputs(args.dump_outputs, dict(live["local"], **live["total"]), rec)     # (the all-reduced counts over this rank's)
     if ctx.force_dist:      # the all-gather of the global line numbering (seeq.c:377) through the shard layer, over RCCL
         dist_info["line_base_of_rank0"] = shard.line_base(live["local"]["nlines"], device=device, force=True)
         dist_info["count_reduce_per_step"] = "all_reduce of (lines, matching lines, hits) over RCCL inside every timed step"

@@ -8,6 +8,7 @@ reference produced for them.  Nothing of the reference's source is stored.
   ref_string_cases.json : seeqStringMatch(pattern, tau, text, options) -> sq->match[]
   ref_cli_cases.json    : reference CLI stdout for small input files
   reads_small.txt       : the shape-R / FASTQ-ish inputs those CLI cases use
+  ref_fuzz_cases.json   : `make_golden.py fuzz` -- the reference's hits for the differential fuzz of test_oracle.py
 """
 import hashlib
 import json
@@ -101,6 +102,22 @@ def string_cases(ref, rng, n):
     return cases
 
 
+FUZZ_OPTIONS = (0, 1, 2, 3, SQ_CONVERT | SQ_BEST, SQ_IGNORE | SQ_ALL, SQ_STREAM | SQ_ALL, SQ_STREAM | SQ_IGNORE | SQ_BEST)
+
+
+def fuzz_cases(ref, rng, n):
+    """The differential fuzz of test_oracle.py: per random pattern / text, the reference's hits under every FUZZ_OPTIONS."""
+    cases = []
+    for _ in range(n):
+        pat = rand_pattern(rng)
+        m = len(plain(pat))
+        tau = rng.randint(0, min(m - 1, rng.choice([0, 1, 2, 3, 5, 8])))
+        text = rand_text(rng, pat, tau, rng.choice([0, 1, 20, 150, 250]))
+        hits = [[list(h) for h in ref.string_match(pat, tau, text, opt)] for opt in FUZZ_OPTIONS]
+        cases.append(dict(pattern=pat, tau=tau, text=text, options=list(FUZZ_OPTIONS), hits=hits))
+    return cases
+
+
 def cli(args, path):
     return subprocess.run([REF_BIN] + args + [path], capture_output=True, text=True).stdout
 
@@ -168,5 +185,12 @@ def main():
     print("string cases:", len(cases), "cli cases:", len(cli_cases))
 
 
+def fuzz_main():
+    cases = fuzz_cases(Reference(), random.Random(77), 400)
+    with open(os.path.join(HERE, "ref_fuzz_cases.json"), "w") as f:
+        json.dump(cases, f, separators=(",", ":"))
+    print("fuzz cases:", len(cases))
+
+
 if __name__ == "__main__":
-    main()
+    fuzz_main() if sys.argv[1:] == ["fuzz"] else main()

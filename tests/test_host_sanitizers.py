@@ -5,13 +5,12 @@ through the reference-generated CLI fixtures and through call sequences of its o
 is a product path: the product library has no CPU matcher (test_capi_host.py::test_no_gpu_fails_loudly).
 
 Also: the reference's own callers (src/seeq-main.c, src/seeq.c, src/seeqmodule.c) compile and link against include/ +
-libseeq_amd.so unchanged -- the drop-in claim of INTEGRATION.md -- whenever /root/reference is present."""
+libseeq_amd.so unchanged -- the drop-in claim of INTEGRATION.md -- wherever oracle/_ref is built."""
 import hashlib
 import os
 import select
 import subprocess
 import sys
-import sysconfig
 import time
 
 import pytest
@@ -203,34 +202,34 @@ def test_cli_with_a_failing_device_boundary(host_cli, cli_cases):
         assert r.returncode == 1 and "error in 'seeqNew()'" in err and r.stdout == b"", (fault, r.returncode, err[-500:])
 
 
-REF_SRC = "/root/reference/src"
+CALLERS = os.path.join(ROOT, "oracle", "_ref", "callers")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference is not present (GPU box)")
+@pytest.mark.skipif(not os.path.exists(os.path.join(CALLERS, "seeq-main.o")),
+                    reason="oracle/_ref not built (make -C oracle ref needs the reference's sources)")
 def test_reference_callers_link_against_the_drop_in(capi):
     """The reference's OWN callers, unmodified, against include/ + libseeq_amd.so: its CLI front end (seeq-main.c) on this
     library's seeq(); its file layer (seeq.c) on this library's libseeq.h entry points; its CPython module (seeqmodule.c).
-    Compiling and linking is the test (running them needs a GPU; the CLI / Python parity tests cover behaviour)."""
+    oracle/Makefile (`ref`) compiles them against include/; linking them with this library is the test (running them needs
+    a GPU; the CLI / Python parity tests cover behaviour)."""
     os.makedirs(BUILD, exist_ok=True)
     libdir = os.path.dirname(capi.LIB_PATH)
-    inc = ["-I" + os.path.join(ROOT, "include")]
     link = ["-L" + libdir, "-lseeq_amd", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    base = ["gcc", "-std=gnu99", "-O2", "-w"]
+    base = ["gcc"]
     # 1. reference main() + this library's seeq()
     exe1 = os.path.join(BUILD, "ref_main_on_drop_in")
-    r = subprocess.run(base + inc + [os.path.join(REF_SRC, "seeq-main.c")] + link + ["-o", exe1], capture_output=True, text=True)
+    r = subprocess.run(base + [os.path.join(CALLERS, "seeq-main.o")] + link + ["-o", exe1], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     # 2. reference main() + reference seeq.c (its own seeqFileMatch loop) + this library's libseeq.h entry points
     exe2 = os.path.join(BUILD, "ref_main_and_file_layer_on_drop_in")
-    r = subprocess.run(base + inc + [os.path.join(REF_SRC, "seeq-main.c"), os.path.join(REF_SRC, "seeq.c")] + link + ["-o", exe2],
+    r = subprocess.run(base + [os.path.join(CALLERS, "seeq-main.o"), os.path.join(CALLERS, "seeq.o")] + link + ["-o", exe2],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
-    # 3. the reference's CPython extension
-    pyinc = sysconfig.get_paths()["include"]
-    if os.path.exists(os.path.join(pyinc, "Python.h")):
+    # 3. the reference's CPython extension (compiled where Python.h exists)
+    mod = os.path.join(CALLERS, "seeqmodule.o")
+    if os.path.exists(mod):
         so = os.path.join(BUILD, "ref_seeqmodule_on_drop_in.so")
-        r = subprocess.run(base + ["-shared", "-fPIC", "-I" + pyinc] + inc + [os.path.join(REF_SRC, "seeqmodule.c")] + link + ["-o", so],
-                           capture_output=True, text=True)
+        r = subprocess.run(base + ["-shared", mod] + link + ["-o", so], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-3000:]
         nm = subprocess.run(["nm", "-D", "--undefined-only", so], capture_output=True, text=True).stdout
         undefined = {ln.split()[-1] for ln in nm.splitlines() if ln.split()[-1].startswith("seeq")}

@@ -1,7 +1,7 @@
 """CPU: the oracle (oracle/seeq_oracle.c) against every golden vector we hold for the path."""
 import hashlib
+import json
 import os
-import random
 
 import numpy as np
 import pytest
@@ -92,19 +92,21 @@ def test_stream_option(oracle):
     assert oracle.string_match(pat, 3, text, SQ_ALL) == []
 
 
-def test_oracle_vs_reference_fuzz(oracle, reference):
-    """Differential fuzz against the reference itself (only where oracle/_ref is built)."""
-    import sys
-    sys.path.insert(0, GOLDEN)
-    from make_golden import plain, rand_pattern, rand_text
-    rng = random.Random(77)
-    for _ in range(400):
-        pat = rand_pattern(rng)
-        m = len(plain(pat))
-        tau = rng.randint(0, min(m - 1, rng.choice([0, 1, 2, 3, 5, 8])))
-        text = rand_text(rng, pat, tau, rng.choice([0, 1, 20, 150, 250]))
-        for opt in (0, 1, 2, 3, 4 | 1, 8 | 2, 0x10 | 2, 0x10 | 8 | 1):
-            assert oracle.string_match(pat, tau, text, opt) == reference.string_match(pat, tau, text, opt)
+def test_oracle_vs_reference_fuzz(oracle):
+    """Differential fuzz against the reference itself: 400 random patterns / texts x 8 options, the reference's hits stored
+    in tests/golden/ref_fuzz_cases.json (make_golden.py fuzz); where oracle/_ref is built, against the live reference too."""
+    from oracle.pyoracle import Reference
+    with open(os.path.join(GOLDEN, "ref_fuzz_cases.json")) as f:
+        fuzz_cases = json.load(f)
+    reference = Reference() if Reference.available() else None
+    assert len(fuzz_cases) == 400
+    for c in fuzz_cases:
+        pat, tau, text = c["pattern"], c["tau"], c["text"]
+        for opt, hits in zip(c["options"], c["hits"]):
+            got = oracle.string_match(pat, tau, text, opt)
+            assert [list(h) for h in got] == hits, (pat, tau, text, opt)
+            if reference is not None:
+                assert got == reference.string_match(pat, tau, text, opt), (pat, tau, text, opt)
 
 
 def test_synth_reads_shape(oracle):
