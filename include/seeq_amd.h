@@ -183,7 +183,7 @@ int seeqdevStringMatch(seeqdev_scan_t * scan, const seeqdev_pattern_t * pat, con
  * that fills the next chunk meanwhile, and one context per GPU, is how seeqFileMatch pipelines its ingest. */
 int seeqdevScanHostBegin(seeqdev_scan_t * scan, const seeqdev_pattern_t * pat, const char * host_text, size_t nbytes,
                          int options, int want);
-/* SEVERAL PATTERNS, ONE TEXT (barcode demultiplexing; the reference names the multi-pattern search as the place where its
+/* SEVERAL PATTERNS, ONE TEXT (barcode sets -- the demultiplexing itself is seeqdevScanRunDemux below; the reference names the multi-pattern search as the place where its
  * algorithm has parallel work, doc/response.tex:358-360, and runs one pattern per scan, seeq.c:307-437).  The text is staged
  * once (seeqdevScanHostMulti) or is already resident (seeqdevScanRunMulti).  A set of 2 .. 32 patterns that has a union
  * automaton (seeq_multi.h: barcodes of 8 .. 12 positions at distance <= 1 do, sixteen at a time) is scanned in ONE walk over
@@ -199,6 +199,40 @@ int seeqdevScanHostMulti(seeqdev_scan_t * scan, const seeqdev_pattern_t * const 
                          int options, int want, seeqdev_counts_t * counts);
 int seeqdevScanMultiRecords(const seeqdev_scan_t * scan, int k, const seeqdev_hit_t ** rec, size_t * nrec);
 int seeqdevScanLastMulti(const seeqdev_scan_t * scan);     /* 1: one walk for all patterns; 0: a scan per pattern */
+
+/* DEMULTIPLEXING: which pattern of a set does each line belong to -- on the device, without the per-pattern records crossing
+ * to the host.  The set is scanned as by seeqdevScanRunMulti (one walk when it can be, else a scan per pattern; SQ_BEST is
+ * implied), and per line the pattern of smallest distance wins, the lowest index on a tie (device.py:assign_best's rule).
+ * The result is one record per ASSIGNED line (a line on which at least one pattern has a record), in ascending line order,
+ * kept on the device: seeqdevScanDemuxDevice (valid until the context's next scan) / seeqdevScanCopyDemux.  The bytes are
+ * the same whichever way the set was scanned.  `margin` = the smallest distance among the OTHER patterns with a record on
+ * the line minus the winner's, saturating at 255; 255 also means that no other pattern matched; 0 means the line is
+ * ambiguous (two patterns tie at the best distance).  `options`: non-DNA mode, MASK_INPUT, SEEQDEV_FASTA, SEEQDEV_SINGLELINE
+ * as in seeqdevScanRunMulti; SQ_ALL / SQ_COUNT, npat < 1 or > 255, NULL pats / pats[k] / sum give EINVAL.  Synchronous.
+ * per_pattern (may be NULL): [npat] lines each pattern won.  Device memory of its own (allocated by a context's first demux,
+ * freed with it): 8 bytes per line of the text and 16 per record; a set scanned pattern by pattern also orders its records
+ * through the context's record workspace.  (The reference has no demultiplexer: an addition of this boundary.) */
+typedef struct {
+   uint32_t line;      /* 1-based, the same numbering as seeqdev_hit_t.line */
+   uint32_t start;
+   uint32_t end;
+   uint16_t dist;      /* the winner's distance */
+   uint8_t  pattern;   /* index of the winner in pats[] */
+   uint8_t  margin;    /* runner-up distance - dist, saturating; 255 = none; 0 = ambiguous */
+} seeqdev_demux_t;     /* 16 bytes */
+
+typedef struct {
+   uint64_t nlines;      /* counted lines, as seeqdev_counts_t.nlines */
+   uint64_t nassigned;   /* records produced */
+   uint64_t nambiguous;  /* of them, margin == 0 */
+} seeqdev_demux_counts_t;
+
+int seeqdevScanRunDemux (seeqdev_scan_t * scan, const seeqdev_pattern_t * const * pats, int npat, const void * d_text, size_t nbytes,
+                         int options, seeqdev_demux_counts_t * sum, uint64_t * per_pattern);
+int seeqdevScanHostDemux(seeqdev_scan_t * scan, const seeqdev_pattern_t * const * pats, int npat, const char * host_text, size_t nbytes,
+                         int options, seeqdev_demux_counts_t * sum, uint64_t * per_pattern);
+const seeqdev_demux_t * seeqdevScanDemuxDevice(const seeqdev_scan_t * scan);
+int seeqdevScanCopyDemux(seeqdev_scan_t * scan, seeqdev_demux_t * host_out, size_t first, size_t n);
 
 /* PACKED READ BATCHES -- 2 bits per base instead of a byte: a quarter of the HBM (and PCIe) traffic of the ASCII scan for
  * read sets that are kept packed anyway (BAM, .2bit, a sequencer's own format).  Layout, all device pointers:

@@ -58,6 +58,15 @@ class seeqdev_textinfo_t(C.Structure):
                 ("probe_peak_bytes", C.c_size_t)]
 
 
+class seeqdev_demux_t(C.Structure):
+    _fields_ = [("line", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("dist", C.c_uint16), ("pattern", C.c_uint8),
+                ("margin", C.c_uint8)]
+
+
+class seeqdev_demux_counts_t(C.Structure):
+    _fields_ = [("nlines", C.c_uint64), ("nassigned", C.c_uint64), ("nambiguous", C.c_uint64)]
+
+
 # Every symbol the three public headers declare (tests check the .so exports all of them).
 EXPORTS = [
     # libseeq.h
@@ -73,6 +82,7 @@ EXPORTS = [
     "seeqdevScanSetLineHint", "seeqdevScanLastPath", "seeqdevScanLastFilter", "seeqdevScanLastPackedQuad", "seeqdevScanCopyOffsets", "seeqdevHostAlloc", "seeqdevTextAlloc", "seeqdevTextAllocInfo", "seeqdevTextAllocFor", "seeqdevTextFree",
     "seeqdevHostFree", "seeqdevStringMatch", "seeqdevScanHostBegin", "seeqdevScanLastCopyMs", "seeqdevPatternDevice",
     "seeqdevScanRunMulti", "seeqdevScanHostMulti", "seeqdevScanMultiRecords", "seeqdevScanLastMulti", "seeqdevScanPacked", "seeqdevPackReads", "seeqdevPackReadsDevice",
+    "seeqdevScanRunDemux", "seeqdevScanHostDemux", "seeqdevScanDemuxDevice", "seeqdevScanCopyDemux",
 ]
 
 
@@ -194,6 +204,16 @@ def lib():
     L.seeqdevScanMultiRecords.restype = C.c_int
     L.seeqdevScanLastMulti.argtypes = [C.c_void_p]
     L.seeqdevScanLastMulti.restype = C.c_int
+    L.seeqdevScanRunDemux.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t, C.c_int, P(seeqdev_demux_counts_t),
+                                      C.POINTER(C.c_uint64)]
+    L.seeqdevScanRunDemux.restype = C.c_int
+    L.seeqdevScanHostDemux.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_size_t, C.c_int, P(seeqdev_demux_counts_t),
+                                       C.POINTER(C.c_uint64)]
+    L.seeqdevScanHostDemux.restype = C.c_int
+    L.seeqdevScanDemuxDevice.argtypes = [C.c_void_p]
+    L.seeqdevScanDemuxDevice.restype = C.c_void_p
+    L.seeqdevScanCopyDemux.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+    L.seeqdevScanCopyDemux.restype = C.c_int
     L.seeqdevScanPacked.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(seeqdev_packed_t), C.c_int, C.c_int]
     L.seeqdevScanPacked.restype = C.c_int
     L.seeqdevPackReads.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]

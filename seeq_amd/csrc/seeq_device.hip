@@ -446,6 +446,8 @@ __global__ void k_single_line(ScanArgs a)
 #include "seeq_pair.h"
 #include "seeq_packed.h"
 #include "seeq_multi.h"
+#include "seeq_demux.h"
+static_assert(sizeof(seeqdev_demux_t) == 16 && sizeof(seeqdev_hit_t) == sizeof(uint4), "demux records are written as uint4");
 #include "seeq_post.h"
 static_assert(STREAM_NW == STREAM_NW_HOST, "waves per k_stream workgroup");
 extern "C" {
@@ -880,6 +882,12 @@ struct seeqdev_scan {
    MultiExact *d_mx, *h_mx; size_t mx_slots, mx_next;      /* per segment the patterns' exact-pass arguments: device copy, pinned ring of mx_slots segments */
    uint32_t *m_scan_ws; size_t cap_m_scan_ws;             /* block sums of the per-pattern scans */
    int       last_multi;                                  /* the last multi scan: 1 = one walk for all patterns, 0 = a scan per pattern */
+   /* seeqdevScanRunDemux (seeq_demux.h): allocated by the first demux call */
+   uint32_t *dm_key, *dm_aux; size_t cap_dm_lines;        /* per line: key, then rank (one walk) or staging slot (a scan per pattern) */
+   uint4    *dm_out; size_t cap_dm_out;                   /* the records (a scan per pattern: first the staging area) */
+   DemuxCnt *d_dmcnt, *h_dmcnt;                           /* h_ pinned */
+   size_t    dm_nrec;                                     /* records of the last demux */
+   uint64_t  dm_nlines;                                   /* its counted lines */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -995,6 +1003,8 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
    }
    { void *pk[] = {s->pk_cand, s->pk_slot, s->pk_coff, s->pk_bmask, s->pk_stage, s->pk_last, s->d_unpack}; for (void *b : pk) if (b) (void)hipFree(b); }
    { void *mw[] = {s->ml_mask, s->ml_first, s->ml_last, s->mp_idx, s->mp_nh, s->m_bsum, s->d_mcnt, s->d_mx, s->m_scan_ws}; for (void *b : mw) if (b) (void)hipFree(b); }
+   { void *dm[] = {s->dm_key, s->dm_aux, s->dm_out, s->d_dmcnt}; for (void *b : dm) if (b) (void)hipFree(b); }
+   if (s->h_dmcnt) (void)hipHostFree(s->h_dmcnt);
    if (s->h_mcnt) (void)hipHostFree(s->h_mcnt);
    if (s->h_mx) (void)hipHostFree(s->h_mx);
    multi_plan_free(s->mplan);
@@ -2512,9 +2522,12 @@ static int multi_grow_host(seeqdev_scan_t *s, size_t n)
    return 0;
 }
 
-/* 0: done; 1: not for this set / text / options (the caller scans pattern by pattern); -1: error */
+static int demux_one_walk(seeqdev_scan_t *s, int npat, uint64_t capR);
+
+/* 0: done; 1: not for this set / text / options (the caller scans pattern by pattern); -1: error.  demux: the records stay on
+   the device and are demultiplexed there (seeqdevScanRunDemux) instead of going to the host. */
 static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *d_text, size_t nbytes,
-                          int options, int want, seeqdev_counts_t *counts)
+                          int options, int want, seeqdev_counts_t *counts, bool demux = false)
 {
    const char *env = getenv("SEEQ_MULTI");
    if (env && !strcmp(env, "sequential")) return 1;
@@ -2579,6 +2592,11 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
       if (!u.overflow && !povf) {
          /* results: counts, then every pattern's records from its region */
          const uint64_t capR = s->cap_records / (uint64_t)npat;
+         if (demux) {
+            rc = demux_one_walk(s, npat, capR) ? -1 : 0;
+            if (rc == 0) s->last_multi = 1;
+            break;
+         }
          s->multi_nrec = 0;
          rc = 0;
          if (want == SEEQDEV_WANT_RECORDS) {
@@ -2680,6 +2698,228 @@ extern "C" int seeqdevScanMultiRecords(const seeqdev_scan_t *s, int k, const see
    if (!s || !rec || !nrec || k < 0 || k >= s->multi_n) { errno = EINVAL; return -1; }
    *rec = s->multi_rec + s->multi_first[k];
    *nrec = s->multi_first[k + 1] - s->multi_first[k];
+   return 0;
+}
+
+/* ========================================================================== */
+/* Demultiplexing: per line the best pattern of a set, on the device (seeq_demux.h)  */
+/* ========================================================================== */
+/* Per-line workspace for nkeys lines (8 bytes per line; allocated by the first demux of a context), keys cleared. */
+static int demux_ws_lines(seeqdev_scan *s, size_t nkeys)
+{
+   if (!s->d_dmcnt && ws_alloc((void **)&s->d_dmcnt, sizeof(DemuxCnt))) return -1;
+   if (!s->h_dmcnt) HIP_TRY(hipHostMalloc((void **)&s->h_dmcnt, sizeof(DemuxCnt), hipHostMallocDefault), ENOMEM);
+   if (nkeys > s->cap_dm_lines) {
+      if (ws_alloc((void **)&s->dm_key, nkeys * sizeof(uint32_t))) return -1;
+      if (ws_alloc((void **)&s->dm_aux, nkeys * sizeof(uint32_t))) return -1;
+      s->cap_dm_lines = nkeys;
+   }
+   const size_t nb = nkeys / SCAN_BLOCK + 2;               /* block sums of the rank scan: the context's scan workspace */
+   if (nb > s->cap_scan_ws) {
+      if (ws_alloc((void **)&s->scan_ws, nb * sizeof(uint32_t))) return -1;
+      s->cap_scan_ws = nb;
+   }
+   if (nkeys) HIP_TRY(hipMemsetAsync(s->dm_key, 0, nkeys * sizeof(uint32_t), s->stream), EIO);
+   HIP_TRY(hipMemsetAsync(s->d_dmcnt, 0, sizeof(DemuxCnt), s->stream), EIO);
+   return 0;
+}
+
+/* Room for n output records; the first `keep` of the old area are carried over (the staging area of a scan per pattern grows). */
+static int demux_ws_out(seeqdev_scan *s, size_t n, size_t keep)
+{
+   if (n < 1) n = 1;
+   if (n <= s->cap_dm_out) return 0;
+   if (keep > s->cap_dm_out) keep = s->cap_dm_out;
+   uint4 *g = NULL;
+   const hipError_t e = hipMalloc((void **)&g, n * sizeof(uint4));
+   if (e != hipSuccess) { (void)hipGetLastError(); return hip_fail(e, "hipMalloc(demux records)", ENOMEM); }
+   if (keep && (hipMemcpyAsync(g, s->dm_out, keep * sizeof(uint4), hipMemcpyDeviceToDevice, s->stream) != hipSuccess ||
+                hipStreamSynchronize(s->stream) != hipSuccess)) {
+      (void)hipFree(g);
+      snprintf(g_last_error, sizeof g_last_error, "hipMemcpyAsync(demux staging)");
+      errno = EIO;
+      return -1;
+   }
+   if (s->dm_out) (void)hipFree(s->dm_out);
+   s->dm_out = g;
+   s->cap_dm_out = n;
+   return 0;
+}
+
+static void demux_fold(seeqdev_scan *s, const seeqdev_hit_t *rec, size_t n, int k, bool stage, uint32_t nkeys)
+{
+   const unsigned grid = (unsigned)((n + DEMUX_WG - 1) / DEMUX_WG);
+   if (stage)
+      hipLaunchKernelGGL(k_demux_fold<true>, dim3(grid), dim3(DEMUX_WG), 0, s->stream, (const uint4 *)rec, (uint32_t)n, (uint32_t)k, s->dm_key,
+                         s->dm_aux, nkeys, s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
+   else
+      hipLaunchKernelGGL(k_demux_fold<false>, dim3(grid), dim3(DEMUX_WG), 0, s->stream, (const uint4 *)rec, (uint32_t)n, (uint32_t)k, s->dm_key,
+                         s->dm_aux, nkeys, s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
+}
+
+/* After the folds: counts, ranks, the records in line order (src: the one walk's records; NULL: the staging area of a scan per
+   pattern), the counters to the host. */
+static int demux_finish(seeqdev_scan *s, uint32_t nkeys, int npat, const DemuxSrc *src, uint32_t nmax)
+{
+   const hipStream_t st = s->stream;
+   const bool stage = src == NULL;
+   if (nkeys) {
+      unsigned grid = (unsigned)((nkeys + DEMUX_WG * 8 - 1) / (DEMUX_WG * 8));
+      if (grid > (unsigned)s->ncu * 8) grid = (unsigned)s->ncu * 8;
+      if (stage) {
+         hipLaunchKernelGGL(k_demux_tally<true>, dim3(grid), dim3(DEMUX_WG), 0, st, (const uint32_t *)s->dm_key, (const uint32_t *)s->dm_aux, nkeys,
+                            s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
+         /* ranks in place of the keys; the records go to the record workspace (free: the last scan's records are folded) */
+         launch_scan<2>(s, st, s->dm_key, s->dm_key, nkeys, nullptr, nkeys, 0, &s->d_dmcnt->nassigned);
+         if (s->cap_records < s->cap_dm_out) {
+            HIP_TRY(hipStreamSynchronize(st), EIO);
+            if (reserve_impl(s, 0, 0, 0, s->cap_dm_out)) return -1;
+         }
+         hipLaunchKernelGGL(k_demux_scatter, dim3(grid), dim3(DEMUX_WG), 0, st, (const uint4 *)s->dm_out, (uint32_t)s->cap_dm_out,
+                            (const uint32_t *)s->dm_key, nkeys, (uint4 *)s->records, (uint32_t)s->cap_records, s->d_dmcnt);
+      } else {
+         hipLaunchKernelGGL(k_demux_tally<false>, dim3(grid), dim3(DEMUX_WG), 0, st, (const uint32_t *)s->dm_key, (const uint32_t *)s->dm_aux, nkeys,
+                            s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
+         launch_scan<2>(s, st, s->dm_key, s->dm_aux, nkeys, nullptr, nkeys, 0, &s->d_dmcnt->nassigned);
+         if (nmax)
+            hipLaunchKernelGGL(k_demux_emit, dim3((nmax + DEMUX_WG - 1) / DEMUX_WG, (unsigned)npat), dim3(DEMUX_WG), 0, st, *src,
+                               (const uint32_t *)s->dm_key, (const uint32_t *)s->dm_aux, nkeys, s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
+      }
+      HIP_TRY(hipGetLastError(), EIO);
+   }
+   HIP_TRY(hipMemcpyAsync(s->h_dmcnt, s->d_dmcnt, sizeof(DemuxCnt), hipMemcpyDeviceToHost, st), EIO);
+   HIP_TRY(hipStreamSynchronize(st), EIO);
+   const DemuxCnt &h = *s->h_dmcnt;
+   if (h.bad || h.nassigned > s->cap_dm_out || (stage && h.slot != h.nassigned)) {
+      snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the demultiplexer (flags %u, %u assigned, %u staged)", h.bad, h.nassigned, h.slot);
+      errno = EIO;
+      return -1;
+   }
+   if (stage && h.nassigned) {
+      HIP_TRY(hipMemcpyAsync(s->dm_out, s->records, (size_t)h.nassigned * sizeof(uint4), hipMemcpyDeviceToDevice, st), EIO);
+      HIP_TRY(hipStreamSynchronize(st), EIO);
+   }
+   s->dm_nrec = h.nassigned;
+   return 0;
+}
+
+/* The one walk is done: pattern k's h_mcnt[k].records records are at records + k * capR, in line order. */
+static int demux_one_walk(seeqdev_scan_t *s, int npat, uint64_t capR)
+{
+   const uint64_t nl = s->h_mcnt[0].lines;
+   if (nl > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
+   const uint32_t nkeys = (uint32_t)nl;
+   s->dm_nlines = nl;
+   if (demux_ws_lines(s, nkeys)) return -1;
+   DemuxSrc src;
+   memset(&src, 0, sizeof src);
+   src.rec = (const uint4 *)s->records;
+   src.stride = capR;
+   size_t total = 0;
+   uint32_t nmax = 0;
+   for (int k = 0; k < npat; k++) {
+      const uint32_t n = (uint32_t)s->h_mcnt[k].records;
+      src.n[k] = n;
+      total += n;
+      if (n > nmax) nmax = n;
+   }
+   if (demux_ws_out(s, total < nkeys ? total : nkeys, 0)) return -1;
+   for (int k = 0; k < npat; k++)
+      if (src.n[k]) demux_fold(s, s->records + (uint64_t)k * capR, src.n[k], k, false, nkeys);
+   return demux_finish(s, nkeys, npat, &src, nmax);
+}
+
+/* A scan per pattern: each pattern's records are folded on the device before the next scan overwrites them. */
+static int demux_per_pattern(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *d_text, size_t nbytes, int options)
+{
+   uint32_t nkeys = 0;
+   size_t sumrec = 0;
+   for (int k = 0; k < npat; k++) {
+      seeqdev_counts_t c;
+      if (seeqdevScanRun(s, pats[k], d_text, nbytes, options, SEEQDEV_WANT_RECORDS)) return -1;
+      if (seeqdevScanFetch(s, &c)) return -1;
+      if (k == 0) {
+         if (c.nlines > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
+         nkeys = (uint32_t)c.nlines;
+         s->dm_nlines = c.nlines;
+         if (demux_ws_lines(s, nkeys)) return -1;
+      } else if (c.nlines != nkeys) {
+         snprintf(g_last_error, sizeof g_last_error, "demultiplexer: pattern %d counted %llu lines, pattern 0 %u", k, (unsigned long long)c.nlines, nkeys);
+         errno = EIO;
+         return -1;
+      }
+      if (!c.nrecords) continue;
+      const size_t staged = sumrec < nkeys ? sumrec : nkeys;       /* at most this many slots are handed out so far */
+      sumrec += (size_t)c.nrecords;
+      if (demux_ws_out(s, sumrec < nkeys ? sumrec : nkeys, staged)) return -1;
+      demux_fold(s, s->records, (size_t)c.nrecords, k, true, nkeys);
+      HIP_TRY(hipGetLastError(), EIO);
+      HIP_TRY(hipStreamSynchronize(s->stream), EIO);          /* the next scan may reallocate the records the fold reads */
+   }
+   return demux_finish(s, nkeys, npat, nullptr, 0);
+}
+
+static int demux_args_ok(const seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *text, size_t nbytes, int options,
+                         const seeqdev_demux_counts_t *sum)
+{
+   if (!s || !pats || npat < 1 || npat > SEEQ_DEMUX_MAX || (!text && nbytes) || !sum || (options & MASK_MATCH) >= SQ_ALL) return 0;
+   for (int k = 0; k < npat; k++) if (!pats[k]) return 0;
+   return 1;
+}
+
+extern "C" int seeqdevScanRunDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *d_text, size_t nbytes,
+                                   int options, seeqdev_demux_counts_t *sum, uint64_t *per_pattern)
+{
+   seeqerr = 0;
+   if (!demux_args_ok(s, pats, npat, d_text, nbytes, options, sum)) { errno = EINVAL; return -1; }
+   if (use_device(s->device)) return -1;
+   const int opts = (options & ~MASK_MATCH) | SQ_BEST;
+   s->dm_nrec = 0;
+   s->dm_nlines = 0;
+   s->multi_n = 0;                                         /* (no multi results on the host: seeqdevScanMultiRecords refuses) */
+   s->multi_nrec = 0;
+   s->last_multi = 0;
+   int rc = multi_one_pass(s, pats, npat, d_text, nbytes, opts, SEEQDEV_WANT_RECORDS, nullptr, true);
+   if (rc == 1) rc = demux_per_pattern(s, pats, npat, d_text, nbytes, opts);
+   /* the borrowed context: nothing of these scans is left to fetch, re-run or copy (their patterns are the caller's) */
+   s->pat = nullptr;
+   s->ran = false;
+   memset(&s->counts, 0, sizeof s->counts);
+   if (rc) { s->dm_nrec = 0; return -1; }
+   const DemuxCnt &h = *s->h_dmcnt;
+   sum->nlines = s->dm_nlines;
+   sum->nassigned = h.nassigned;
+   sum->nambiguous = h.ambiguous;
+   if (per_pattern) for (int k = 0; k < npat; k++) per_pattern[k] = h.per_pat[k];
+   return 0;
+}
+
+extern "C" int seeqdevScanHostDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const char *host_text, size_t nbytes,
+                                    int options, seeqdev_demux_counts_t *sum, uint64_t *per_pattern)
+{
+   seeqerr = 0;
+   if (!demux_args_ok(s, pats, npat, host_text, nbytes, options, sum)) { errno = EINVAL; return -1; }
+   if (use_device(s->device)) return -1;
+   if (nbytes > s->cap_text) {
+      const size_t cap = nbytes + (nbytes >> 2) + 4096;
+      if (ws_alloc((void **)&s->d_text, cap)) return -1;
+      s->cap_text = cap;
+   }
+   if (nbytes) HIP_TRY(hipMemcpyAsync(s->d_text, host_text, nbytes, hipMemcpyHostToDevice, s->stream), EIO);
+   s->avg_text = NULL;                                     /* new contents behind the same pointer: sample again */
+   return seeqdevScanRunDemux(s, pats, npat, s->d_text, nbytes, options, sum, per_pattern);
+}
+
+extern "C" const seeqdev_demux_t *seeqdevScanDemuxDevice(const seeqdev_scan_t *s) { return s ? (const seeqdev_demux_t *)s->dm_out : NULL; }
+
+extern "C" int seeqdevScanCopyDemux(seeqdev_scan_t *s, seeqdev_demux_t *host_out, size_t first, size_t n)
+{
+   seeqerr = 0;
+   if (!s || (!host_out && n) || first > s->dm_nrec || n > s->dm_nrec - first) { errno = EINVAL; return -1; }
+   if (n == 0) return 0;
+   if (use_device(s->device)) return -1;
+   HIP_TRY(hipMemcpyAsync(host_out, s->dm_out + first, n * sizeof(seeqdev_demux_t), hipMemcpyDeviceToHost, s->stream), EIO);
+   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
    return 0;
 }
 

@@ -281,6 +281,62 @@ class Scanner:
         return self._multi(patterns, lambda arr, n, cnts: self._lib.seeqdevScanRunMulti(self._h, arr, n, C.c_void_p(t.data_ptr()), t.numel(),
                                                                                      options, want, cnts), want, copy)
 
+    # ---- demultiplexing on the device (include/seeq_amd.h: seeqdevScanRunDemux / seeqdevScanHostDemux) ----
+    def _demux(self, patterns, call, copy):
+        n = len(patterns)
+        arr = (C.c_void_p * n)(*[C.cast(p.handle, C.c_void_p) for p in patterns])
+        cnt = _capi.seeqdev_demux_counts_t()
+        per = (C.c_uint64 * n)()
+        _check(call(arr, n, C.byref(cnt), per))
+        res = dict(nlines=int(cnt.nlines), nassigned=int(cnt.nassigned), nambiguous=int(cnt.nambiguous), assigned=[int(x) for x in per],
+                   records=None)
+        if copy:
+            res["records"] = self.demux_records(int(cnt.nassigned))
+        return res
+
+    def demux_records(self, n, first=0):
+        """Copy records [first, first + n) of the last demultiplex to the host -> structured array of DEMUX_DTYPE."""
+        out = np.zeros(n, dtype=DEMUX_DTYPE)
+        _check(self._lib.seeqdevScanCopyDemux(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def demux_device_ptr(self):
+        """Device address of the last demultiplex's records (seeqdev_demux_t, in line order; valid until this Scanner's next scan)."""
+        return self._lib.seeqdevScanDemuxDevice(self._h)
+
+    def demux_host(self, patterns, data, options=0):
+        """data: bytes, staged once.  Per line the best pattern of the set, demultiplexed on the device -> dict: nlines, nassigned,
+        nambiguous, assigned (lines won per pattern), records (one per assigned line, in line order; DEMUX_DTYPE)."""
+        return self._demux(patterns, lambda arr, n, cnt, per: self._lib.seeqdevScanHostDemux(self._h, arr, n, data, len(data), options, cnt, per), True)
+
+    def demux_tensor(self, patterns, t, options=0, copy=True):
+        """t: torch uint8 CUDA tensor (contiguous), resident.  As demux_host; copy=False leaves the records on the device
+        (records None: demux_device_ptr / demux_records)."""
+        return self._demux(patterns, lambda arr, n, cnt, per: self._lib.seeqdevScanRunDemux(self._h, arr, n, C.c_void_p(t.data_ptr()), t.numel(),
+                                                                                         options, cnt, per), copy)
+
+
+# One record of seeqdevScanRunDemux (seeq_amd.h: seeqdev_demux_t, 16 bytes).
+DEMUX_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("dist", "<u2"), ("pattern", "u1"), ("margin", "u1")])
+
+
+def demux_dense(result, nlines):
+    """A demux_host / demux_tensor result (copy=True) -> the dense per-line arrays assign_best returns:
+    (which [nlines] int32, -1 = no pattern matched; dist [nlines] int32, -1 there; start, end [nlines] int64)."""
+    rec = result["records"]
+    if rec is None:
+        raise ValueError("demux_dense needs the records: demultiplex with copy=True")
+    which = np.full(nlines, -1, dtype=np.int32)
+    dist = np.full(nlines, -1, dtype=np.int32)
+    start = np.zeros(nlines, dtype=np.int64)
+    end = np.zeros(nlines, dtype=np.int64)
+    ln = rec["line"].astype(np.int64) - 1
+    which[ln] = rec["pattern"]
+    dist[ln] = rec["dist"]
+    start[ln] = rec["start"]
+    end[ln] = rec["end"]
+    return which, dist, start, end
+
 
 def assign_best(results, nlines):
     """Demultiplexing rule on top of a multi-pattern SQ_BEST scan: per line the pattern with the smallest distance
