@@ -176,7 +176,7 @@ def test_bench_launches_its_own_ranks(gpu):
     import subprocess
     env = dict(os.environ, SEEQ_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--reads", "300000", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--reads", "300000", "--steps", "2",
                         "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-per-call", "--check-lines", "100000"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -200,14 +200,14 @@ def test_bench_launches_its_own_ranks(gpu):
 
 @pytest.mark.gpu
 def test_bench_default_line_sections_at_small_sizes(gpu):
-    """The sections of the default `bench.py` line, shrunk: the headline (text from seeqdevTextAllocFor, `first_allocation` beside it), the
+    """The sections of the `bench.py --full` line, shrunk: the headline (text from seeqdevTextAllocFor, `first_allocation` beside it), the
     FASTQ shape (k_pair under SQ_FAIL / SQ_CONVERT since round 5, counts = the reference binary's, prefix records = the oracle's) and
     BASELINE configs[4] as a section with its own roofline and full check; `results` and `roofline` close the line."""
     import json
     import subprocess
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "1500000", "--steps", "3", "--warmup", "1", "--first-steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--reads", "1500000", "--steps", "3", "--warmup", "1", "--first-steps", "2",
                         "--placement-candidates", "3", "--fastq-records", "400000", "--cfg5-reads", "700000", "--cpu-sample", "200000",
                         "--no-e2e", "--no-per-call", "--no-packed", "--no-multi", "--no-cli", "--check-lines", "200000"],
                        capture_output=True, text=True, env=env, timeout=900)
@@ -244,7 +244,7 @@ def test_bench_rccl_process_group_over_one_rank(gpu):
         env.pop(k, None)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--reads", "2000000",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-dist", "--reads", "2000000",
                         "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-per-call", "--no-packed", "--no-cli",
                         "--no-multi", "--no-cfg5", "--no-fastq", "--check-lines", "100000"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
@@ -282,7 +282,7 @@ def test_two_real_segments_full_size_parity(gpu, workload, reads):
     import subprocess
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--reads", str(reads), "--steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", workload, "--reads", str(reads), "--steps", "1",
                         "--warmup", "0", "--first-steps", "2", "--no-cpu-baseline", "--no-e2e", "--no-per-call", "--no-cfg5", "--no-fastq", "--no-multi", "--no-packed"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
