@@ -85,6 +85,7 @@ static constexpr int WG = 256;           /* 4 waves */
 static constexpr int TILE = 16384;       /* bytes per newline-index workgroup: 64 B per thread */
 static constexpr size_t FUSED_MIN_TILE = 512;    /* smallest text tile / region of the one-pass kernels */
 static constexpr int STREAM_NW_HOST = 16;         /* = STREAM_NW (seeq_stream.h): waves per k_stream workgroup */
+static constexpr uint32_t STREAM_CH_HOST = 128;    /* bytes per lane of k_stream / k_pair */
 static constexpr size_t MAX_FUSED_GRID = 16384;   /* upper bound of the waves (= hit slices) of a persistent scan grid */
 static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate the line length */
 
@@ -145,7 +146,7 @@ __global__ void k_index_finalize(ScanArgs a)
    uint32_t n = c->seg_nlines;
    if (a.first_seg && a.nbytes > 0) n += 1;
    if (n > a.cap_lines) {
-      atomicOr(&c->overflow, 1u);
+      atomicOr(&c->overflow, OVF_LINES);
       if (n > c->need_lines) c->need_lines = n;
       n = 0;                       /* later kernels of this segment do nothing */
    } else if (n > c->need_lines) {
@@ -342,7 +343,7 @@ __global__ void k_seg_mid(ScanArgs a)
    uint32_t nhl = c->seg_nhitlines;
    if (nhl > c->need_hitlines) c->need_hitlines = nhl;
    if (nhl > a.cap_hitlines) {
-      atomicOr(&c->overflow, 2u);
+      atomicOr(&c->overflow, OVF_HITLINES);
       nhl = 0;
       c->seg_nhitlines = 0;      /* totals of this run are void anyway */
    }
@@ -363,7 +364,7 @@ __global__ __launch_bounds__(WG) void k_exact(ScanArgs a)
    const Counters *c = a.cnt;
    const uint32_t nhl = c->seg_nhitlines;
    const int match_opt = a.options & 3;
-   if (MODE == SQ_MODE_EMIT && (c->overflow & 4u)) return;
+   if (MODE == SQ_MODE_EMIT && (c->overflow & OVF_RECORDS)) return;
    const uint32_t stride = gridDim.x * WG;
    for (uint32_t k = blockIdx.x * WG + threadIdx.x; k < nhl; k += stride) {
       const uint64_t off = a.seg_base + a.hit_start[k];
@@ -394,7 +395,7 @@ __global__ __launch_bounds__(WG) void k_exact(ScanArgs a)
 __global__ __launch_bounds__(WG) void k_rec_offsets(ScanArgs a)
 {
    const Counters *c = a.cnt;
-   if (c->overflow & 4u) return;
+   if (c->overflow & OVF_RECORDS) return;
    const uint32_t nhl = c->seg_nhitlines;
    const bool all = (a.options & 3) == SQ_ALL || a.use_nh;
    const uint32_t stride = gridDim.x * WG;
@@ -912,9 +913,9 @@ struct seeqdev_scan {
    bool no_stream_nd;          /* SQ_CONVERT / SQ_IGNORE: the text has non-DNA bytes, k_stream (exact for clean text only) is off */
    bool no_leaders;            /* long lines with many hits: a leader's fresh start lay inside the walk before it -- every line stays with one lane */
    bool no_window;             /* k_pair's candidates: a line had candidates on both sides of a segment seam -- whole lines are scanned */
-   int  fallback_ttl;          /* scans left before the three fall-back flags above are dropped and the fast path is tried again (one text with a
+   int  fallback_ttl;          /* scans left before the fall-back flags above are dropped and the fast path is tried again (one text with a
                                   long line or foreign bytes must not slow a long-lived context down for good) */
-   bool sample_dirty;          /* the sampled prefix holds more than one byte outside the alphabet per 4 KB: k_pair stays out */
+   bool sample_dirty;          /* the sampled prefix holds more than one byte outside the alphabet per 4 KB: FASTA input stays off k_pair */
    unsigned sample_age;        /* runs since the line-length sample was taken (a reused buffer may hold other text by now) */
 };
 
@@ -1253,7 +1254,7 @@ static int occupancy_of(seeqdev_scan *s, const void *fn, int threads, size_t lds
    return per_cu;
 }
 
-static int multi_post(seeqdev_scan *s, const ScanArgs &ua, hipStream_t st);
+static int multi_post(seeqdev_scan *s, const ScanPlan &plan, const ScanArgs &ua, hipStream_t st);
 
 /* what the planner (seeq_plan.h) needs to know of the pattern's automata, and how it asks for one that has not been tried yet */
 static void pattern_automata(const seeqdev_pattern *p, PlanAutomata *au)
@@ -1275,23 +1276,57 @@ static void plan_ensure(void *ctx, int which, int complete_only, PlanAutomata *a
 /* ---- a run of seeqdevScanRun, in pieces (round 5: run_segments was one function of 385 lines; the decisions had moved to seeq_plan.h in round 4,
         what is left executes the plan):  run_setup -- the plan, the kernel instance and its grid, the EQ tables, the profiling events;
         seg_onepass -- a segment's one-pass scan kernel (k_pair / k_stream / k_direct) and the ordering of its hit slices;
-        seg_index_forward<W> -- the generic path's newline index and k_forward<W>;  seg_post<W> -- the exact pass and the records ---- */
+        seg_index_forward<W> -- the generic path's newline index and k_forward<W>;  seg_post<W> -- the exact pass and the records.
+        They read the scan from the context (s->pat, s->options, ...), its plan from r.plan; SegRun holds what run_setup derives beside it ---- */
 struct SegRun {
-   const seeqdev_pattern *pat;
-   int       options, want;
    ScanPlan  plan;
-   int       fw, nw;                  /* column words of the one-pass kernels; waves per workgroup of the scan kernel */
+   int       nw;                      /* waves per workgroup of the scan kernel: one hit slice per wave of the grid */
    uint32_t  tile_bytes;
-   unsigned  fused_grid, nslices, grid_lines;
+   unsigned  fused_grid, grid_lines;
    const void *stream_fn;             /* the k_stream / k_pair instance of this run */
    size_t    dfa_lds, seg_bytes, nseg;
 };
 
-/* EQ[dir][byte][fw]: the top-aligned Peq column of the byte's class, or a flag (reference seeqcore.h:89-111 folded with the non-DNA option,
-   libseeq.c:223-228,265-270) -- uploaded when the pattern or the options changed since the context's last scan */
-static int eq_tables_upload(seeqdev_scan *s, const seeqdev_pattern *pat, int options, int fw)
+/* Workgroups of WG threads over n entries, at most per_cu per CU (the grids of the per-line and hit-list kernels) */
+static unsigned capped_grid(const seeqdev_scan *s, size_t n, size_t per_cu)
 {
-   if (s->eq_pat_id == pat->id && s->eq_options == options) return 0;
+   const size_t blocks = (n + WG - 1) / WG, cap = (size_t)s->ncu * per_cu;
+   const unsigned g = (unsigned)(blocks < cap ? blocks : cap);
+   return g ? g : 1;
+}
+
+/* Profiling: four events for each of nseg segments (s->prof_segs: the segments of this run that record them) */
+static int prof_events(seeqdev_scan *s, size_t nseg)
+{
+   s->prof_segs = 0;
+   if (!s->prof) return 0;
+   if (nseg > s->nev_seg) {
+      hipEvent_t *g = (hipEvent_t *)realloc(s->ev, 4 * nseg * sizeof(hipEvent_t));
+      if (!g) { seeqerr = 0; errno = ENOMEM; return -1; }
+      s->ev = g;
+      for (size_t i = 4 * s->nev_seg; i < 4 * nseg; i++) HIP_TRY(hipEventCreate(&s->ev[i]), EIO);
+      s->nev_seg = nseg;
+   }
+   s->prof_segs = nseg;
+   return 0;
+}
+
+/* The flags of seg_end_body: 1 = the hits come from nh[], 2 = nh[] holds 0/1 verdicts (a superset's lines, hits not counted per line) */
+static int seg_end_flags(bool need_nh, bool superset, bool nh_is_count) { return (need_nh ? 1 : 0) | (superset && !nh_is_count ? 2 : 0); }
+
+/* k_verify's variant (seeq_verify.h) and a.fin: k_nh_top ends the segment with `seg_flags` unless k_exact1's EMIT pass follows (SQ_ALL
+   records: k_emit1 works from what k_nh_top saved) */
+static int verify_variant(int want, int options, bool nh_is_count, int seg_flags, uint32_t *fin)
+{
+   const int var = (want == SEEQDEV_WANT_RECORDS && (options & 3) == SQ_BEST) ? VERIFY_BEST : nh_is_count ? VERIFY_ALL : VERIFY_ANY;
+   *fin = (want == SEEQDEV_WANT_RECORDS && var == VERIFY_ALL) ? 0u : 1u + (uint32_t)seg_flags;
+   return var;
+}
+
+/* EQ[dir][byte][fw] of one pattern (512 x fw words): the top-aligned Peq column of the byte's class, or a flag (reference seeqcore.h:89-111
+   folded with the non-DNA option, libseeq.c:223-228,265-270) */
+static void eq_fill(uint32_t *tab, const seeqdev_pattern *pat, int options, int fw)
+{
    const int Wp = pat->words;
    for (int dir = 0; dir < 2; dir++)
       for (int b = 0; b < 256; b++) {
@@ -1304,10 +1339,17 @@ static int eq_tables_upload(seeqdev_scan *s, const seeqdev_pattern *pat, int opt
          } else {
             v = cls == SQC_TERM ? FUSED_FLAG_TERM : FUSED_FLAG_SKIP;
          }
-         uint32_t *dst = s->h_eqtab + (size_t)(dir * 256 + b) * fw;
+         uint32_t *dst = tab + (size_t)(dir * 256 + b) * fw;
          dst[0] = (uint32_t)v;
          if (fw == 2) dst[1] = (uint32_t)(v >> 32);
       }
+}
+
+/* The context's EQ tables: uploaded when the pattern or the options changed since its last scan */
+static int eq_tables_upload(seeqdev_scan *s, const seeqdev_pattern *pat, int options, int fw)
+{
+   if (s->eq_pat_id == pat->id && s->eq_options == options) return 0;
+   eq_fill(s->h_eqtab, pat, options, fw);
    /* third table, k_stream's Myers mode: the forward table with the newline marked (flag bits 0-1 = 3) */
    memcpy(s->h_eqtab + (size_t)512 * fw, s->h_eqtab, (size_t)256 * fw * sizeof(uint32_t));
    s->h_eqtab[(size_t)512 * fw + (size_t)'\n' * fw] |= 3u;
@@ -1322,172 +1364,119 @@ static int eq_tables_upload(seeqdev_scan *s, const seeqdev_pattern *pat, int opt
 static int run_setup(seeqdev_scan *s, SegRun &r)
 {
    const seeqdev_pattern *pat = s->pat;
-   const int options = s->options, want = s->want;
-   const bool fasta = (options & SEEQDEV_FASTA) != 0;
-   const bool single = (options & SEEQDEV_SINGLELINE) != 0;
-   const size_t nbytes = s->nbytes;
-
-
-   const int ncu = s->ncu;
-   const ScanKnobs &kn = s->knobs;
-
-   const size_t line_blocks = (s->cap_lines + WG - 1) / WG;
-   unsigned grid_lines = (unsigned)(line_blocks < (size_t)ncu * 16 ? line_blocks : (size_t)ncu * 16);
-   if (grid_lines == 0) grid_lines = 1;
+   const bool fasta = (s->options & SEEQDEV_FASTA) != 0, single = (s->options & SEEQDEV_SINGLELINE) != 0;
+   r.grid_lines = capped_grid(s, s->cap_lines, 16);
 
    /* ---- the plan (seeq_plan.h: a pure function of the pattern, the options, the text's line length and this context's fall-back
            flags); the rest of this function executes it ---- */
    PlanIn pin;
    memset(&pin, 0, sizeof pin);
-   pin.wlen = pat->wlen; pin.tau = pat->tau; pin.options = options; pin.want = want;
+   pin.wlen = pat->wlen; pin.tau = pat->tau; pin.options = s->options; pin.want = s->want;
    pin.avg_line = s->avg_line; pin.line_hint = s->line_hint; pin.force_path = s->force_path;
    pin.no_stream = s->no_stream; pin.force_ll = s->force_ll; pin.no_stream_nd = s->no_stream_nd; pin.no_window = s->no_window;
    pin.no_leaders = s->no_leaders; pin.sample_dirty = s->sample_dirty; pin.multi_active = s->multi_active;
-   pin.seg_bytes = s->seg_bytes; pin.kn = &kn;
+   pin.seg_bytes = s->seg_bytes; pin.kn = &s->knobs;
    PlanAutomata au;
    pattern_automata(pat, &au);
    r.plan = seeq_plan_scan(pin, au, plan_ensure, const_cast<seeqdev_pattern *>(pat));
    const ScanPlan &plan = r.plan;
-   if (kn.explain) seeq_plan_print(stderr, pin, au, plan);
+   if (s->knobs.explain) seeq_plan_print(stderr, pin, au, plan);
    if (plan.rc) return plan.rc;
-   const int fw = plan.fw;
-   const bool use_stream = plan.use_stream, use_pair = plan.use_pair, use_myers = plan.use_myers, filter = plan.filter, use_fused = plan.use_fused;
-   const int stream_ch = 128;                 /* bytes per lane of k_stream / k_pair */
-   const int stream_wu = plan.stream_wu;
-   uint32_t tile_bytes = 0;
-   unsigned fused_grid = 1;
-   int nw = 4;
-   unsigned nslices = 1;                      /* hit slices: one per wave */
-   const void *stream_fn = nullptr;
-   const bool stream_ll = plan.stream_ll;
-   const int stream_sub = plan.stream_sub;    /* 0, 1: SQ_CONVERT ('N' for non-DNA bytes), 2: SQ_IGNORE (skip bytes) */
-   size_t dfa_lds = 0;
-   if (use_fused) {
-      if (use_stream) {
-         nw = STREAM_NW;
-         tile_bytes = 64u * (uint32_t)stream_ch;
-         /* the k_stream instance of this scan: <warm-up dwords, FASTA, long lines, SUB> */
+   const int fw = plan.fw, stream_wu = plan.stream_wu;
+   if (plan.use_fused) {
+      if (plan.use_stream) {
+         r.nw = STREAM_NW;
+         r.tile_bytes = 64u * STREAM_CH_HOST;
+         /* the k_stream instance of this scan: <warm-up dwords, FASTA, long lines, SUB> (stream_sub 0, 1: SQ_CONVERT ('N' for non-DNA bytes),
+            2: SQ_IGNORE (skip bytes)) */
 #define SEEQ_STREAM_FN(...) (stream_wu == 4 ? (const void *)k_stream<4, __VA_ARGS__> : stream_wu == 6 ? (const void *)k_stream<6, __VA_ARGS__> \
                                                                                                       : (const void *)k_stream<8, __VA_ARGS__>)
-         stream_fn = stream_sub == 2 ? SEEQ_STREAM_FN(false, false, 2)
-                   : stream_sub ? (stream_ll ? SEEQ_STREAM_FN(false, true, 1) : SEEQ_STREAM_FN(false, false, 1))
-                   : stream_ll ? (fasta ? SEEQ_STREAM_FN(true, true) : SEEQ_STREAM_FN(false, true))
-                   : fasta ? SEEQ_STREAM_FN(true, false) : SEEQ_STREAM_FN(false, false);
+         r.stream_fn = plan.stream_sub == 2 ? SEEQ_STREAM_FN(false, false, 2)
+                     : plan.stream_sub ? (plan.stream_ll ? SEEQ_STREAM_FN(false, true, 1) : SEEQ_STREAM_FN(false, false, 1))
+                     : plan.stream_ll ? (fasta ? SEEQ_STREAM_FN(true, true) : SEEQ_STREAM_FN(false, true))
+                     : fasta ? SEEQ_STREAM_FN(true, false) : SEEQ_STREAM_FN(false, false);
 #undef SEEQ_STREAM_FN
-         dfa_lds = ((size_t)pat->sdfa_rows * 16 + 15) & ~(size_t)15;
-         if (use_myers) {
+         r.dfa_lds = ((size_t)pat->sdfa_rows * 16 + 15) & ~(size_t)15;
+         if (plan.use_myers) {
 #define SEEQ_MYERS_FN(FA, MY) (stream_wu == 16 ? (const void *)k_stream<16, FA, true, 0, MY> : (const void *)k_stream<32, FA, true, 0, MY>)
-            stream_fn = fw == 1 ? (fasta ? SEEQ_MYERS_FN(true, 1) : SEEQ_MYERS_FN(false, 1)) : (fasta ? SEEQ_MYERS_FN(true, 2) : SEEQ_MYERS_FN(false, 2));
+            r.stream_fn = fw == 1 ? (fasta ? SEEQ_MYERS_FN(true, 1) : SEEQ_MYERS_FN(false, 1)) : (fasta ? SEEQ_MYERS_FN(true, 2) : SEEQ_MYERS_FN(false, 2));
 #undef SEEQ_MYERS_FN
-            dfa_lds = (size_t)256 * fw * sizeof(uint32_t);
+            r.dfa_lds = (size_t)256 * fw * sizeof(uint32_t);
          }
-         if (use_pair) {
+         if (plan.use_pair) {
 #define SEEQ_PAIR_FN(...) (stream_wu == 4 ? (const void *)k_pair<4, __VA_ARGS__> : stream_wu == 5 ? (const void *)k_pair<5, __VA_ARGS__> : stream_wu == 6 ? (const void *)k_pair<6, __VA_ARGS__> \
                           : stream_wu == 7 ? (const void *)k_pair<7, __VA_ARGS__> : (const void *)k_pair<8, __VA_ARGS__>)
-            stream_fn = fasta ? SEEQ_PAIR_FN(true) : plan.ig ? SEEQ_PAIR_FN(false, true) : plan.pair_ll ? SEEQ_PAIR_FN(false, false, true) : SEEQ_PAIR_FN(false);
-            dfa_lds = (size_t)pat->pair_units * 16;
+            r.stream_fn = fasta ? SEEQ_PAIR_FN(true) : plan.ig ? SEEQ_PAIR_FN(false, true) : plan.pair_ll ? SEEQ_PAIR_FN(false, false, true) : SEEQ_PAIR_FN(false);
+            r.dfa_lds = (size_t)pat->pair_units * 16;
 #undef SEEQ_PAIR_FN
          }
-         int per_cu = occupancy_of(s, stream_fn, 64 * nw, dfa_lds);
-         if (per_cu < 0) return -1;
-         fused_grid = (unsigned)(ncu * per_cu);
-         if ((size_t)fused_grid * nw > MAX_FUSED_GRID) fused_grid = (unsigned)(MAX_FUSED_GRID / nw);
-         nslices = fused_grid * nw;                         /* one hit slice per wave */
       } else {
-         nw = 4;
+         r.nw = 4;
          double want = s->avg_line * 63.5;                /* <= 64 lines per region: one per lane */
          if (want < 512) want = 512;
          if (want > DIRECT_MAXRR * 1024) want = DIRECT_MAXRR * 1024;      /* (k_direct reads a region in at most DIRECT_MAXRR rounds of 1 KiB: lines that average more than 258 bytes
                                                                               once made regions of 16 KiB + 48 bytes, whose last 48 bytes no round looked at -- profiles/ignore_fuzz.py) */
-         tile_bytes = ((uint32_t)want) & ~15u;
-         if (kn.tile_bytes >= 512 && kn.tile_bytes <= DIRECT_MAXRR * 1024) tile_bytes = (uint32_t)kn.tile_bytes & ~15u;
-         int per_cu = occupancy_of(s, fw == 1 ? (const void *)k_direct<4, 1> : (const void *)k_direct<4, 2>, 256, 0);
-         if (per_cu < 0) return -1;
-         fused_grid = (unsigned)(ncu * per_cu);
-         if ((size_t)fused_grid * nw > MAX_FUSED_GRID) fused_grid = (unsigned)(MAX_FUSED_GRID / nw);
-         nslices = fused_grid * nw;                         /* one hit slice per wave */
+         r.tile_bytes = ((uint32_t)want) & ~15u;
+         if (s->knobs.tile_bytes >= 512 && s->knobs.tile_bytes <= DIRECT_MAXRR * 1024) r.tile_bytes = (uint32_t)s->knobs.tile_bytes & ~15u;
       }
-      if (eq_tables_upload(s, pat, options, fw)) return -1;
+      const void *fn = plan.use_stream ? r.stream_fn : fw == 1 ? (const void *)k_direct<4, 1> : (const void *)k_direct<4, 2>;
+      const int per_cu = occupancy_of(s, fn, 64 * r.nw, r.dfa_lds);
+      if (per_cu < 0) return -1;
+      r.fused_grid = (unsigned)(s->ncu * per_cu);
+      if ((size_t)r.fused_grid * r.nw > MAX_FUSED_GRID) r.fused_grid = (unsigned)(MAX_FUSED_GRID / r.nw);
+      if (eq_tables_upload(s, pat, s->options, fw)) return -1;
    }
-   const bool use_direct = plan.use_direct;
    s->last_path = plan.path;
-   s->last_filter = filter;
-   const bool superset = plan.superset;                  /* the scan kernel's hit lines are candidates: nh[] decides */
-   const bool need_nh = plan.need_nh, nh_is_count = plan.nh_is_count;
+   s->last_filter = plan.filter;
 
-   const size_t seg_bytes = single ? (nbytes ? nbytes : 1) : s->seg_bytes;
+   const size_t nbytes = s->nbytes;
+   r.seg_bytes = single ? (nbytes ? nbytes : 1) : s->seg_bytes;
    if (single && nbytes > 0xFFFF0000ull) { seeqerr = 0; errno = E2BIG; return -1; }
-   const size_t nseg = nbytes ? (nbytes + seg_bytes - 1) / seg_bytes : 0;
-   s->prof_segs = 0;
-   if (s->prof && nseg > s->nev_seg) {
-      hipEvent_t *g = (hipEvent_t *)realloc(s->ev, 4 * nseg * sizeof(hipEvent_t));
-      if (!g) { seeqerr = 0; errno = ENOMEM; return -1; }
-      s->ev = g;
-      for (size_t i = 4 * s->nev_seg; i < 4 * nseg; i++) HIP_TRY(hipEventCreate(&s->ev[i]), EIO);
-      s->nev_seg = nseg;
-   }
-   if (s->prof) s->prof_segs = nseg;
-   if (s->prof && nseg > s->cap_clk_probe) {
+   r.nseg = nbytes ? (nbytes + r.seg_bytes - 1) / r.seg_bytes : 0;
+   if (prof_events(s, r.nseg)) return -1;
+   if (s->prof && r.nseg > s->cap_clk_probe) {
       if (s->clk_probe) (void)hipHostFree(s->clk_probe);
       s->clk_probe = nullptr; s->cap_clk_probe = 0;
-      if (hipHostMalloc((void **)&s->clk_probe, nseg * 4 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess) s->cap_clk_probe = nseg;
+      if (hipHostMalloc((void **)&s->clk_probe, r.nseg * 4 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess) s->cap_clk_probe = r.nseg;
    }
-   if (s->prof && s->clk_probe) memset(s->clk_probe, 0, nseg * 4 * sizeof(unsigned long long));
-   s->clk_valid = s->prof && s->clk_probe && use_pair && use_fused;
+   if (s->prof && s->clk_probe) memset(s->clk_probe, 0, r.nseg * 4 * sizeof(unsigned long long));
+   s->clk_valid = s->prof && s->clk_probe && plan.use_pair && plan.use_fused;
    /* (Tried: the post-pass of segment k on a second stream under k_pair of segment k + 1, k_pair on one workgroup per CU --
       it is as fast there.  The post-pass kernels do run beside it, and take 3 to 14 times as long as alone: they are
       made of scattered loads and the memory system is what k_pair saturates.  Net: +2 % .. -3 % per step.  Not kept;
       tag r03-experiment-overlap-postpass, profiles/r03/overlap_trace.txt.) */
-   r.pat = pat; r.options = options; r.want = want;
-   r.fw = fw; r.nw = nw; r.tile_bytes = tile_bytes; r.fused_grid = fused_grid; r.nslices = nslices; r.grid_lines = grid_lines;
-   r.stream_fn = stream_fn; r.dfa_lds = dfa_lds; r.seg_bytes = seg_bytes; r.nseg = nseg;
-   (void)use_direct; (void)superset; (void)need_nh; (void)nh_is_count; (void)use_myers;
    return 0;
 }
 
 /* a segment's one-pass scan kernel + the ordering of its hit slices: newline handling, forward scan and per-tile compaction in ONE kernel */
 static int seg_onepass(seeqdev_scan *s, const SegRun &r, ScanArgs &a, size_t sg, hipEvent_t *ev, bool &order2, uint32_t &stream_ntiles)
 {
-   const seeqdev_pattern *pat = r.pat;
-   const int options = r.options, want = r.want, match_opt = r.options & 3, fw = r.fw, ncu = s->ncu;
    const ScanPlan &plan = r.plan;
-   const bool fasta = (options & SEEQDEV_FASTA) != 0, single = (options & SEEQDEV_SINGLELINE) != 0;
-   const bool use_stream = plan.use_stream, use_pair = plan.use_pair, use_myers = plan.use_myers, filter = plan.filter, use_fused = plan.use_fused, use_direct = plan.use_direct;
-   const bool stream_ll = plan.stream_ll, superset = plan.superset, need_nh = plan.need_nh, nh_is_count = plan.nh_is_count;
-   const int stream_sub = plan.stream_sub, stream_ch = 128, nw = r.nw;
-   const uint32_t tile_bytes = r.tile_bytes;
-   const unsigned fused_grid = r.fused_grid, nslices = r.nslices, grid_lines = r.grid_lines;
-   const void *stream_fn = r.stream_fn;
-   const size_t dfa_lds = r.dfa_lds, nbytes = s->nbytes;
-   Counters *c = s->d_cnt;
-   seeqdev_scan::OnePassWs &ow = s->ow;
+   const seeqdev_pattern *pat = s->pat;
+   const seeqdev_scan::OnePassWs &ow = s->ow;
    hipStream_t st = s->stream;
-   (void)pat; (void)want; (void)match_opt; (void)fw; (void)ncu; (void)fasta; (void)single; (void)use_stream; (void)use_pair; (void)use_myers; (void)filter; (void)use_fused;
-   (void)use_direct; (void)stream_ll; (void)superset; (void)need_nh; (void)nh_is_count; (void)stream_sub; (void)stream_ch; (void)nw; (void)tile_bytes; (void)fused_grid;
-   (void)nslices; (void)grid_lines; (void)stream_fn; (void)dfa_lds; (void)nbytes; (void)c; (void)ow; (void)st;
 
-   /* ---- fused path: newline index + forward scan + per-tile compaction in ONE kernel ---- */
    FusedArgs f;
    memset(&f, 0, sizeof f);
-   f.text = a.text; f.nbytes = nbytes; f.seg_base = a.seg_base; f.seg_len = a.seg_len; f.first_seg = a.first_seg;
-   f.tile_bytes = tile_bytes;
-   f.ntiles = (uint32_t)(((uint64_t)a.seg_len + tile_bytes - 1) / tile_bytes);
+   f.text = a.text; f.nbytes = s->nbytes; f.seg_base = a.seg_base; f.seg_len = a.seg_len; f.first_seg = a.first_seg;
+   f.tile_bytes = r.tile_bytes;
+   f.ntiles = (uint32_t)(((uint64_t)a.seg_len + r.tile_bytes - 1) / r.tile_bytes);
    stream_ntiles = f.ntiles;
    f.eqtab = s->d_eqtab; f.peq = pat->d_peq;
-   f.m = pat->wlen; f.tau = pat->tau; f.options = options; f.want = want;
+   f.m = pat->wlen; f.tau = pat->tau; f.options = s->options; f.want = s->want;
    f.tile_cl = ow.tile_cl; f.tile_hits = ow.tile_hits; f.tmp = ow.tmp; f.cap_tmp = (uint32_t)s->cap_hitlines;
-   f.wg_hits = ow.wg_hits; f.wg_part = ow.wg_part; f.wg_lastnl = stream_ll ? ow.wg_lastnl : nullptr;   /* only the window walk (long lines) needs it */
+   f.wg_hits = ow.wg_hits; f.wg_part = ow.wg_part; f.wg_lastnl = plan.stream_ll ? ow.wg_lastnl : nullptr;   /* only the window walk (long lines) needs it */
    f.tile_dirty = f.wg_lastnl ? ow.tile_dirty : nullptr;
    f.tile_dmask = f.wg_lastnl ? ow.tile_dmask : nullptr;
-   f.cnt = c;
-   f.clk_probe = (s->prof && s->clk_probe && use_pair) ? s->clk_probe + 4 * sg : nullptr;
+   f.cnt = s->d_cnt;
+   f.clk_probe = (s->prof && s->clk_probe && plan.use_pair) ? s->clk_probe + 4 * sg : nullptr;
    uint32_t pos_bias = 0;
-   if (use_stream) {
-      f.dfa = stream_sub == 2 ? pat->d_sdfa_skip : plan.ll_restart ? pat->d_sdfa_restart : pat->d_sdfa; f.dfa_rows = pat->sdfa_rows; f.dfa_final_base = pat->sdfa_final_base;
+   if (plan.use_stream) {
+      f.dfa = plan.stream_sub == 2 ? pat->d_sdfa_skip : plan.ll_restart ? pat->d_sdfa_restart : pat->d_sdfa; f.dfa_rows = pat->sdfa_rows; f.dfa_final_base = pat->sdfa_final_base;
       f.ll_filter = plan.ll_restart ? 2u : plan.ll_filter ? 1u : 0u;      /* (2: the restart table -- a chain that accepted inside its warm-up window names its first byte) */
       f.skip_thr = plan.skip_thr;
-      if (use_pair) { f.dfa = pat->d_pair; f.dfa_rows = pat->pair_units; f.dfa_final_base = 0; f.pair = 1; f.ig_thr = plan.ig ? (uint32_t)(pat->wlen - pat->tau) : 0u; }
-      if (use_myers) { f.dfa = (const uint16_t *)(s->d_eqtab + (size_t)512 * fw); f.dfa_rows = (uint32_t)(64 * fw); f.dfa_final_base = 0; f.pair = 2; }
+      if (plan.use_pair) { f.dfa = pat->d_pair; f.dfa_rows = pat->pair_units; f.dfa_final_base = 0; f.pair = 1; f.ig_thr = plan.ig ? (uint32_t)(pat->wlen - pat->tau) : 0u; }
+      if (plan.use_myers) { f.dfa = (const uint16_t *)(s->d_eqtab + (size_t)512 * plan.fw); f.dfa_rows = (uint32_t)(64 * plan.fw); f.dfa_final_base = 0; f.pair = 2; }
       /* A hit line can start before the segment: hit offsets of this segment are relative to seg_base - pos_bias */
       uint64_t room = 0xFFFFFFF0ull - a.seg_len;
       if (room > ((uint64_t)1 << 30)) room = (uint64_t)1 << 30;
@@ -1495,15 +1484,15 @@ static int seg_onepass(seeqdev_scan *s, const SegRun &r, ScanArgs &a, size_t sg,
       f.pos_bias = pos_bias;
    }
    if (ev) { HIP_TRY(hipEventRecord(ev[0], st), EIO); HIP_TRY(hipEventRecord(ev[1], st), EIO); }
-   unsigned fgrid = fused_grid;                     /* persistent: workgroups without a tile just publish zeros */
-   const unsigned nsl = nslices;
+   /* persistent grid (workgroups without a tile just publish zeros), one hit slice per wave */
+   const unsigned nsl = r.fused_grid * r.nw;
    f.slice_cap = f.cap_tmp / nsl;
-   if (use_stream) {
+   if (plan.use_stream) {
       void *kargs[] = {&f};
-      HIP_TRY(hipLaunchKernel(stream_fn, dim3(fgrid), dim3(64 * (unsigned)nw), kargs, dfa_lds, st), EIO);
+      HIP_TRY(hipLaunchKernel(r.stream_fn, dim3(r.fused_grid), dim3(64 * (unsigned)r.nw), kargs, r.dfa_lds, st), EIO);
    }
-   else if (use_direct && fw == 2) hipLaunchKernelGGL((k_direct<4, 2>), dim3(fgrid), dim3(256), 0, st, f);
-   else hipLaunchKernelGGL((k_direct<4, 1>), dim3(fgrid), dim3(256), 0, st, f);
+   else if (plan.use_direct && plan.fw == 2) hipLaunchKernelGGL((k_direct<4, 2>), dim3(r.fused_grid), dim3(256), 0, st, f);
+   else hipLaunchKernelGGL((k_direct<4, 1>), dim3(r.fused_grid), dim3(256), 0, st, f);
    if (ev) HIP_TRY(hipEventRecord(ev[2], st), EIO);
    /* read-length lines behind k_pair / k_stream: the three launches of seeq_order.h; else (long lines, k_direct) the seven of before */
    const uint32_t order_nb = (f.ntiles + SEEQ_ORDER_BLOCK - 1) / SEEQ_ORDER_BLOCK;
@@ -1523,24 +1512,23 @@ static int seg_onepass(seeqdev_scan *s, const SegRun &r, ScanArgs &a, size_t sg,
          a.ig_bmask = best == 3 ? 0xDEu : 0xDFu;           /* T: U and either case too */
       }
    }
+   const unsigned rgrid = nsl / 4 + 1 < 2048 ? nsl / 4 + 1 : 2048;       /* one wave per slice, strided */
    if (order2) {
-      const unsigned rgrid = nsl / 4 + 1 < 2048 ? nsl / 4 + 1 : 2048;       /* one wave per slice, strided */
       seeq_launch_tiles_post(st, f, (uint32_t)nsl, s->scan_ws, order_nb);
       seeq_launch_order(rgrid, st, f, (uint32_t)nsl, (const uint32_t *)s->scan_ws, order_nb, s->ent);
    }
    else hipLaunchKernelGGL(k_fused_post, dim3(1), dim3(256), 0, st, f, (uint32_t)nsl);
-   if (!order2 && (want != SEEQDEV_WANT_COUNTLINES || superset)) {
-      launch_scanset(s, st, f.tile_hits, f.tile_cl, f.tile_dirty, f.ntiles, nullptr, nullptr, f.tile_dirty ? &c->seg_dirty_tiles : nullptr);
-      const unsigned rgrid = nsl / 4 + 1 < 2048 ? nsl / 4 + 1 : 2048;       /* one wave per slice, strided */
-      if (use_stream) hipLaunchKernelGGL(k_stream_reorder, dim3(rgrid), dim3(256), 0, st, f, (uint32_t)nsl, s->hit_start, s->hit_line, s->nh, s->hit_col);
+   if (!order2 && (s->want != SEEQDEV_WANT_COUNTLINES || plan.superset)) {
+      launch_scanset(s, st, f.tile_hits, f.tile_cl, f.tile_dirty, f.ntiles, nullptr, nullptr, f.tile_dirty ? &s->d_cnt->seg_dirty_tiles : nullptr);
+      if (plan.use_stream) hipLaunchKernelGGL(k_stream_reorder, dim3(rgrid), dim3(256), 0, st, f, (uint32_t)nsl, s->hit_start, s->hit_line, s->nh, s->hit_col);
       else hipLaunchKernelGGL(k_fused_reorder, dim3(rgrid), dim3(256), 0, st, f, (uint32_t)nsl, s->hit_start, s->hit_line);
    }
    a.seg_base -= pos_bias;                           /* the exact pass addresses lines through hit_start */
    a.pos_bias = pos_bias;
-   a.tile_dirty = f.tile_dirty; a.tile_dmask = f.tile_dmask; a.stream_ntiles = f.ntiles; a.stream_tile_bytes = tile_bytes;
+   a.tile_dirty = f.tile_dirty; a.tile_dmask = f.tile_dmask; a.stream_ntiles = f.ntiles; a.stream_tile_bytes = r.tile_bytes;
    /* the exact pass walks candidate windows instead of whole lines where lines are long (sampled average);
       read-length lines are scanned whole -- the bookkeeping of the walk costs more than it saves there */
-   a.stream_ch = stream_ll ? (uint32_t)stream_ch : 0u;
+   a.stream_ch = plan.stream_ll ? STREAM_CH_HOST : 0u;
    a.walk_ext = plan.walk_ext; a.ll_restart = plan.ll_restart ? 1u : 0u;
    return 0;
 }
@@ -1549,27 +1537,11 @@ static int seg_onepass(seeqdev_scan *s, const SegRun &r, ScanArgs &a, size_t sg,
 template <int W>
 static int seg_index_forward(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipEvent_t *ev)
 {
-   const seeqdev_pattern *pat = r.pat;
-   const int options = r.options, want = r.want, match_opt = r.options & 3, fw = r.fw, ncu = s->ncu;
-   const ScanPlan &plan = r.plan;
-   const bool fasta = (options & SEEQDEV_FASTA) != 0, single = (options & SEEQDEV_SINGLELINE) != 0;
-   const bool use_stream = plan.use_stream, use_pair = plan.use_pair, use_myers = plan.use_myers, filter = plan.filter, use_fused = plan.use_fused, use_direct = plan.use_direct;
-   const bool stream_ll = plan.stream_ll, superset = plan.superset, need_nh = plan.need_nh, nh_is_count = plan.nh_is_count;
-   const int stream_sub = plan.stream_sub, stream_ch = 128, nw = r.nw;
-   const uint32_t tile_bytes = r.tile_bytes;
-   const unsigned fused_grid = r.fused_grid, nslices = r.nslices, grid_lines = r.grid_lines;
-   const void *stream_fn = r.stream_fn;
-   const size_t dfa_lds = r.dfa_lds, nbytes = s->nbytes;
    Counters *c = s->d_cnt;
-   seeqdev_scan::OnePassWs &ow = s->ow;
    hipStream_t st = s->stream;
-   (void)pat; (void)want; (void)match_opt; (void)fw; (void)ncu; (void)fasta; (void)single; (void)use_stream; (void)use_pair; (void)use_myers; (void)filter; (void)use_fused;
-   (void)use_direct; (void)stream_ll; (void)superset; (void)need_nh; (void)nh_is_count; (void)stream_sub; (void)stream_ch; (void)nw; (void)tile_bytes; (void)fused_grid;
-   (void)nslices; (void)grid_lines; (void)stream_fn; (void)dfa_lds; (void)nbytes; (void)c; (void)ow; (void)st;
-
    /* ---- K0: newline index ---- */
    if (ev) HIP_TRY(hipEventRecord(ev[0], st), EIO);
-   if (single) {
+   if (s->options & SEEQDEV_SINGLELINE) {
       hipLaunchKernelGGL(k_single_line, dim3(1), dim3(1), 0, st, a);
    } else {
       hipLaunchKernelGGL(k_nl_count, dim3(a.ntiles), dim3(WG), 0, st, a);
@@ -1579,11 +1551,11 @@ static int seg_index_forward(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipE
    }
    /* ---- K1: forward scan ---- */
    if (ev) HIP_TRY(hipEventRecord(ev[1], st), EIO);
-   hipLaunchKernelGGL(k_forward<W>, dim3(grid_lines), dim3(WG), 0, st, a);
+   hipLaunchKernelGGL(k_forward<W>, dim3(r.grid_lines), dim3(WG), 0, st, a);
    if (ev) HIP_TRY(hipEventRecord(ev[2], st), EIO);
    /* ---- K2: ranks of hit lines (and FASTA headers) ---- */
    launch_scan<1>(s, st, a.hitmask, a.wave_off, s->cap_chunks, &c->seg_nlines, 63u, 6u, &c->seg_nhitlines);
-   if (fasta) launch_scan<1>(s, st, a.hdrmask, a.hdr_off, s->cap_chunks, &c->seg_nlines, 63u, 6u, &c->seg_nheaders);
+   if (s->options & SEEQDEV_FASTA) launch_scan<1>(s, st, a.hdrmask, a.hdr_off, s->cap_chunks, &c->seg_nlines, 63u, 6u, &c->seg_nheaders);
    return 0;
 }
 
@@ -1592,45 +1564,29 @@ static int seg_index_forward(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipE
 template <int W>
 static int seg_post(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipEvent_t *ev, bool order2, uint32_t stream_ntiles)
 {
-   const seeqdev_pattern *pat = r.pat;
-   const int options = r.options, want = r.want, match_opt = r.options & 3, fw = r.fw, ncu = s->ncu;
    const ScanPlan &plan = r.plan;
-   const bool fasta = (options & SEEQDEV_FASTA) != 0, single = (options & SEEQDEV_SINGLELINE) != 0;
-   const bool use_stream = plan.use_stream, use_pair = plan.use_pair, use_myers = plan.use_myers, filter = plan.filter, use_fused = plan.use_fused, use_direct = plan.use_direct;
-   const bool stream_ll = plan.stream_ll, superset = plan.superset, need_nh = plan.need_nh, nh_is_count = plan.nh_is_count;
-   const int stream_sub = plan.stream_sub, stream_ch = 128, nw = r.nw;
-   const uint32_t tile_bytes = r.tile_bytes;
-   const unsigned fused_grid = r.fused_grid, nslices = r.nslices, grid_lines = r.grid_lines;
-   const void *stream_fn = r.stream_fn;
-   const size_t dfa_lds = r.dfa_lds, nbytes = s->nbytes;
+   const int want = s->want, fw = plan.fw;
    Counters *c = s->d_cnt;
-   seeqdev_scan::OnePassWs &ow = s->ow;
    hipStream_t st = s->stream;
-   (void)pat; (void)want; (void)match_opt; (void)fw; (void)ncu; (void)fasta; (void)single; (void)use_stream; (void)use_pair; (void)use_myers; (void)filter; (void)use_fused;
-   (void)use_direct; (void)stream_ll; (void)superset; (void)need_nh; (void)nh_is_count; (void)stream_sub; (void)stream_ch; (void)nw; (void)tile_bytes; (void)fused_grid;
-   (void)nslices; (void)grid_lines; (void)stream_fn; (void)dfa_lds; (void)nbytes; (void)c; (void)ow; (void)st;
 
    /* ---- K3: compaction ---- */
-   if (!use_fused) hipLaunchKernelGGL(k_compact, dim3(grid_lines), dim3(WG), 0, st, a);
-   if (!use_fused) hipLaunchKernelGGL(k_seg_mid, dim3(1), dim3(1), 0, st, a);   /* the fused paths: done by k_fused_post */
-   const size_t hit_blocks = (s->cap_hitlines + WG - 1) / WG;
-   unsigned grid_hits = (unsigned)(hit_blocks < (size_t)ncu * 16 ? hit_blocks : (size_t)ncu * 16);
-   if (grid_hits == 0) grid_hits = 1;
+   if (!plan.use_fused) hipLaunchKernelGGL(k_compact, dim3(r.grid_lines), dim3(WG), 0, st, a);
+   if (!plan.use_fused) hipLaunchKernelGGL(k_seg_mid, dim3(1), dim3(1), 0, st, a);   /* the fused paths: done by k_fused_post */
+   const unsigned grid_hits = capped_grid(s, s->cap_hitlines, 16);
    if (order2) seeq_launch_bounds2(grid_hits, st, a, s->ent, s->hit_col);
-   else if (use_stream) hipLaunchKernelGGL(k_stream_bounds, dim3(grid_hits), dim3(256), 0, st, a, s->hit_col,
-                                      (const uint32_t *)ow.tile_cl, stream_ntiles, tile_bytes);   /* hit position -> line start; repeats dropped */
+   else if (plan.use_stream) hipLaunchKernelGGL(k_stream_bounds, dim3(grid_hits), dim3(256), 0, st, a, s->hit_col,
+                                           (const uint32_t *)s->ow.tile_cl, stream_ntiles, r.tile_bytes);   /* hit position -> line start; repeats dropped */
    if (s->multi_active) {
       /* several patterns: the candidate list is the union's -- pattern sets per line, a list per pattern, the exact pass per pattern */
-      { const int mr = multi_post(s, a, st); if (mr > 0) return -2; if (mr) return -1; }      /* (1: a launch was refused -- a scan per pattern) */
+      { const int mr = multi_post(s, plan, a, st); if (mr > 0) return -2; if (mr) return -1; }      /* (1: a launch was refused -- a scan per pattern) */
       hipLaunchKernelGGL(k_seg_end, dim3(1), dim3(1), 0, st, a, 3);
       if (ev) HIP_TRY(hipEventRecord(ev[3], st), EIO);
       HIP_TRY(hipGetLastError(), EIO);
       return 1;
    }
    /* long lines, every hit counted: candidates far behind the one before them get a lane of their own (seeq_stream.h, leaders) */
-   const bool lead_best = plan.lead_best, leaders = plan.leaders;
    const uint32_t lead_wback = a.skip_back > 32u ? a.skip_back : 32u;
-   if (leaders) {
+   if (plan.leaders) {
       if (s->cap_hitlines > s->cap_lead) {
          if (ws_alloc((void **)&s->lead_fidx, s->cap_hitlines * sizeof(uint32_t))) return -1;
          if (ws_alloc((void **)&s->lead_flag, s->cap_hitlines * sizeof(uint32_t))) return -1;
@@ -1641,15 +1597,16 @@ static int seg_post(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipEvent_t *e
       const unsigned nbl = (unsigned)(s->cap_hitlines / LEAD_BLOCK + 1);
       hipLaunchKernelGGL(k_lead_reduce, dim3(nbl), dim3(256), 0, st, a, s->scan_ws);
       hipLaunchKernelGGL(k_lead_top, dim3(1), dim3(256), 0, st, a, s->scan_ws);
-      hipLaunchKernelGGL(k_lead_apply, dim3(nbl), dim3(256), 0, st, a, (const uint32_t *)s->hit_col, (const uint32_t *)s->scan_ws, s->lead_fidx, s->lead_flag, ow.tmp, lead_wback, lead_best ? s->lead_key : (unsigned long long *)nullptr);
+      hipLaunchKernelGGL(k_lead_apply, dim3(nbl), dim3(256), 0, st, a, (const uint32_t *)s->hit_col, (const uint32_t *)s->scan_ws, s->lead_fidx, s->lead_flag, s->ow.tmp, lead_wback, plan.lead_best ? s->lead_key : (unsigned long long *)nullptr);
       a.walk_end = s->lead_wend;
       /* SQ_BEST: COUNT has to walk every group itself (and leave each group's best hit in the cache) instead of trusting the hit
          list and leaving the scan to EMIT, one lane per line */
-      if (lead_best) a.filter = 1u;
-      hipLaunchKernelGGL(k_lead_commit, dim3(grid_hits), dim3(256), 0, st, a, s->hit_col, (const uint4 *)ow.tmp);
+      if (plan.lead_best) a.filter = 1u;
+      hipLaunchKernelGGL(k_lead_commit, dim3(grid_hits), dim3(256), 0, st, a, s->hit_col, (const uint4 *)s->ow.tmp);
    }
-   const uint32_t *hcol = use_stream ? s->hit_col : nullptr;      /* first-hit columns: the exact pass may skip ahead */
-   uint4 *ecache = (use_fused && need_nh && want == SEEQDEV_WANT_RECORDS) ? ow.tmp : nullptr;   /* COUNT -> EMIT */
+   const uint32_t *hcol = plan.use_stream ? s->hit_col : nullptr;      /* first-hit columns: the exact pass may skip ahead */
+   uint4 *ecache = (plan.use_fused && plan.need_nh && want == SEEQDEV_WANT_RECORDS) ? s->ow.tmp : nullptr;   /* COUNT -> EMIT */
+   const uint32_t *eqp = (const uint32_t *)s->d_eqtab;
    /* (Tried behind k_pair: a lane-queue kernel -- a wave owns 256 .. 512 hit-list entries staged in LDS and a lane that has
       finished its line takes the next entry at the next 64-byte block -- 22 % fewer instructions than k_exact1 COUNT, and
       slower, 296 against 257 us per segment: at 4 waves per SIMD the per-block loads of a lane are not hidden.  Not kept;
@@ -1658,27 +1615,21 @@ static int seg_post(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipEvent_t *e
    /* behind the filters (every hit line is a candidate) on text where no byte is skipped: k_verify (seeq_verify.h) -- the lean
       two-phase exact pass with the scan of its counts inside; the EMIT pass behind it ends the segment */
    bool emitted = false;                                /* the records are out (k_emit1) */
-   const bool verify = plan.verify;
-   const int seg_flags = (need_nh ? 1 : 0) | (superset && !nh_is_count ? 2 : 0);
-   if (verify) {
-      const bool count_any = want != SEEQDEV_WANT_COUNTMATCH && !(want == SEEQDEV_WANT_RECORDS && match_opt == SQ_ALL);
-      const int var = (want == SEEQDEV_WANT_RECORDS && match_opt == SQ_BEST) ? VERIFY_BEST : count_any ? VERIFY_ANY : VERIFY_ALL;
+   if (plan.verify) {
+      const int var = verify_variant(want, s->options, plan.nh_is_count, seg_end_flags(plan.need_nh, plan.superset, plan.nh_is_count), &a.fin);
       a.nh_sum = s->nh_sum;
-      a.nz_sum = superset && nh_is_count ? s->nh_sum + (s->cap_hitlines / 256 + 2) : nullptr;
-      /* k_nh_top ends the segment unless k_exact1's EMIT pass follows (SQ_ALL records): k_emit1 works from what k_nh_top saved */
-      a.fin = (want == SEEQDEV_WANT_RECORDS && var == VERIFY_ALL) ? 0u : 1u + (uint32_t)seg_flags;
+      a.nz_sum = plan.superset && plan.nh_is_count ? s->nh_sum + (s->cap_hitlines / 256 + 2) : nullptr;
       /* behind a partition filter every part of an occurrence reports: more than half of the entries are repeats of their line, and
          k_verify packs them away, 512 entries per workgroup (seeq_verify.h); behind a prefix automaton it does not pay */
-      a.vrange = (use_pair ? pat->pair_parts > 1 : pat->sdfa_parts > 1) ? 512u : 0u;
-      seeq_launch_verify(fw, var, grid_hits, st, a, (const uint32_t *)s->d_eqtab, hcol, ecache);
+      a.vrange = (plan.use_pair ? s->pat->pair_parts > 1 : s->pat->sdfa_parts > 1) ? 512u : 0u;
+      seeq_launch_verify(fw, var, grid_hits, st, a, eqp, hcol, ecache);
       if (want == SEEQDEV_WANT_RECORDS && var != VERIFY_ALL) seeq_launch_emit1(grid_hits, st, a, ecache);
       else if (want == SEEQDEV_WANT_RECORDS && ecache)      /* SQ_ALL: the first records from the cache, the others from the overflow lists */
-         seeq_launch_emit_all(fw, grid_hits, grid_hits, st, a, (const uint32_t *)s->d_eqtab, hcol, ecache);
+         seeq_launch_emit_all(fw, grid_hits, grid_hits, st, a, eqp, hcol, ecache);
       emitted = want == SEEQDEV_WANT_RECORDS && (var != VERIFY_ALL || ecache);
    }
-   else if (need_nh) {
-      if (use_fused) {
-         const uint32_t *eqp = (const uint32_t *)s->d_eqtab;
+   else if (plan.need_nh) {
+      if (plan.use_fused) {
    #define SEEQ_COUNT1(WW, WK) hipLaunchKernelGGL((k_exact1<SQ_MODE_COUNT, WW, -1, WK>), dim3(grid_hits), dim3(WG), 0, st, a, eqp, hcol, ecache)
          if (fw == 2) { if (a.stream_ch) SEEQ_COUNT1(2, true); else SEEQ_COUNT1(2, false); }
          else { if (a.stream_ch) SEEQ_COUNT1(1, true); else SEEQ_COUNT1(1, false); }
@@ -1686,23 +1637,22 @@ static int seg_post(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipEvent_t *e
       }
       else hipLaunchKernelGGL((k_exact<W, SQ_MODE_COUNT>), dim3(grid_hits), dim3(WG), 0, st, a);
       /* lines with >= 1 verified hit: with 0/1 verdicts that is the scan total (seg_nrec) -- no extra pass */
-      if (leaders) {
+      if (plan.leaders) {
          hipLaunchKernelGGL(k_lead_check, dim3(grid_hits), dim3(256), 0, st, a, (const uint32_t *)s->hit_col, (const uint32_t *)s->lead_flag, lead_wback);
-         if (lead_best) {
+         if (plan.lead_best) {
             hipLaunchKernelGGL(k_lead_best, dim3(grid_hits), dim3(256), 0, st, a, (const uint32_t *)s->lead_fidx, s->lead_key, (const uint4 *)ecache, 0);
             hipLaunchKernelGGL(k_lead_best, dim3(grid_hits), dim3(256), 0, st, a, (const uint32_t *)s->lead_fidx, s->lead_key, (const uint4 *)ecache, 1);
          }
          else hipLaunchKernelGGL(k_lead_lines, dim3(grid_hits < 512 ? grid_hits : 512), dim3(256), 0, st, a, (const uint32_t *)s->lead_fidx, s->lead_flag);
       }
-      else if (superset && nh_is_count) hipLaunchKernelGGL(k_count_nonzero, dim3(grid_hits < 512 ? grid_hits : 512), dim3(WG), 0, st, a);
+      else if (plan.superset && plan.nh_is_count) hipLaunchKernelGGL(k_count_nonzero, dim3(grid_hits < 512 ? grid_hits : 512), dim3(WG), 0, st, a);
       launch_scan<0>(s, st, a.nh, a.nh, s->cap_hitlines, &c->seg_nhitlines, 0u, 0u, &c->seg_nrec);
    }
    /* ---- K5: records ---- */
    if (want == SEEQDEV_WANT_RECORDS && !emitted) {
-      if (!verify) hipLaunchKernelGGL(k_rec_check, dim3(1), dim3(1), 0, st, a);      /* (k_verify's last workgroup did) */
-      if (use_fused) {
-         const uint32_t *eqp = (const uint32_t *)s->d_eqtab;
-         const int mo = (options & 3) == SQ_COUNT ? SQ_FIRST : (options & 3);
+      if (!plan.verify) hipLaunchKernelGGL(k_rec_check, dim3(1), dim3(1), 0, st, a);      /* (k_verify's last workgroup did) */
+      if (plan.use_fused) {
+         const int mo = (s->options & 3) == SQ_COUNT ? SQ_FIRST : (s->options & 3);
    #define SEEQ_EMIT1(WW, OO, WK) hipLaunchKernelGGL((k_exact1<SQ_MODE_EMIT, WW, OO, WK>), dim3(grid_hits), dim3(WG), 0, st, a, eqp, hcol, ecache)
          if (a.stream_ch) {
             if (fw == 2) { if (mo == SQ_BEST) SEEQ_EMIT1(2, SQ_BEST, true); else SEEQ_EMIT1(2, -1, true); }
@@ -1725,53 +1675,50 @@ template <int W>
 static int run_segments(seeqdev_scan *s)
 {
    Counters *c = s->d_cnt;
-   HIP_TRY(hipMemsetAsync(c, 0, sizeof(Counters), s->stream), EIO);
+   hipStream_t st = s->stream;
+   HIP_TRY(hipMemsetAsync(c, 0, sizeof(Counters), st), EIO);
    SegRun r;
    memset(&r, 0, sizeof r);
    { const int rc = run_setup(s, r); if (rc) return rc; }
-   const seeqdev_pattern *pat = r.pat;
    const ScanPlan &plan = r.plan;
-   const int options = r.options, want = r.want;
-   const size_t nbytes = s->nbytes, seg_bytes = r.seg_bytes, nseg = r.nseg;
-   const bool use_stream = plan.use_stream, use_fused = plan.use_fused, filter = plan.filter, superset = plan.superset, need_nh = plan.need_nh, nh_is_count = plan.nh_is_count;
-   for (size_t sg = 0; sg < nseg; sg++) {
-
+   const seeqdev_pattern *pat = s->pat;
+   const size_t nbytes = s->nbytes;
+   for (size_t sg = 0; sg < r.nseg; sg++) {
       hipEvent_t *ev = s->prof ? s->ev + 4 * sg : NULL;
       uint32_t stream_ntiles = 0;
       bool order2 = false;                                /* the hit list is made by seeq_order.h's kernels */
-      hipStream_t st = s->stream;
       ScanArgs a;
       memset(&a, 0, sizeof a);
       a.text = (const uint8_t *)s->text;
       a.nbytes = nbytes;
-      a.seg_base = (uint64_t)sg * seg_bytes;
-      a.seg_len = (uint32_t)((nbytes - a.seg_base) < seg_bytes ? (nbytes - a.seg_base) : seg_bytes);
+      a.seg_base = (uint64_t)sg * r.seg_bytes;
+      a.seg_len = (uint32_t)((nbytes - a.seg_base) < r.seg_bytes ? (nbytes - a.seg_base) : r.seg_bytes);
       a.first_seg = sg == 0;
       a.peq = pat->d_peq;
-      a.m = pat->wlen; a.tau = pat->tau; a.options = options; a.want = want;
+      a.m = pat->wlen; a.tau = pat->tau; a.options = s->options; a.want = s->want;
       a.line_start = s->line_start; a.cap_lines = (uint32_t)s->cap_lines;
       a.tile_cnt = s->tile_cnt; a.ntiles = (a.seg_len + TILE - 1) / TILE;
       a.hitmask = s->hitmask; a.hdrmask = s->hdrmask; a.wave_off = s->wave_off; a.hdr_off = s->hdr_off;
       a.hit_start = s->hit_start; a.hit_line = s->hit_line; a.cap_hitlines = (uint32_t)s->cap_hitlines; a.nh = s->nh;
       a.records = s->records; a.cap_records = s->cap_records; a.rec_off = s->rec_off;
-      a.use_nh = need_nh ? (use_stream ? 3u : 1u) : 0u;
-      a.filter = filter ? 1u : 0u;
+      a.use_nh = plan.need_nh ? (plan.use_stream ? 3u : 1u) : 0u;
+      a.filter = plan.filter ? 1u : 0u;
       a.skip_back = plan.skip_back;
       a.window_ok = plan.window_ok ? 1u : 0u;
       a.cnt = c;
 
-      if (use_fused) { if (seg_onepass(s, r, a, sg, ev, order2, stream_ntiles)) return -1; }
+      if (plan.use_fused) { if (seg_onepass(s, r, a, sg, ev, order2, stream_ntiles)) return -1; }
       else if (seg_index_forward<W>(s, r, a, ev)) return -1;
-      if (want != SEEQDEV_WANT_COUNTLINES || superset) {
+      if (s->want != SEEQDEV_WANT_COUNTLINES || plan.superset) {
          const int pr = seg_post<W>(s, r, a, ev, order2, stream_ntiles);
          if (pr < 0) return pr;
          if (pr > 0) continue;
       }
-      if (!a.fin) hipLaunchKernelGGL(k_seg_end, dim3(1), dim3(1), 0, st, a, (need_nh ? 1 : 0) | (superset && !nh_is_count ? 2 : 0));      /* (a.fin: the segment's last launch ended it) */
+      if (!a.fin) hipLaunchKernelGGL(k_seg_end, dim3(1), dim3(1), 0, st, a, seg_end_flags(plan.need_nh, plan.superset, plan.nh_is_count));      /* (a.fin: the segment's last launch ended it) */
       if (ev) HIP_TRY(hipEventRecord(ev[3], st), EIO);
       HIP_TRY(hipGetLastError(), EIO);
    }
-   HIP_TRY(hipMemcpyAsync(s->h_cnt, c, sizeof(Counters), hipMemcpyDeviceToHost, s->stream), EIO);
+   HIP_TRY(hipMemcpyAsync(s->h_cnt, c, sizeof(Counters), hipMemcpyDeviceToHost, st), EIO);
    return 0;
 }
 
@@ -1787,6 +1734,7 @@ static int run_packed(seeqdev_scan *s)
    const int options = s->options, want = s->want;
    const int match_opt = options & 3;
    const bool nh_is_count = want == SEEQDEV_WANT_COUNTMATCH || (want == SEEQDEV_WANT_RECORDS && match_opt == SQ_ALL);
+   const int seg_flags = seg_end_flags(true, true, nh_is_count);      /* (every hit line is a candidate: nh[] decides) */
    const int fw = pat->wlen <= FUSED_MAX_WLEN ? 1 : 2;
    Counters *c = s->d_cnt;
    hipStream_t st = s->stream;
@@ -1842,19 +1790,9 @@ static int run_packed(seeqdev_scan *s)
       const size_t nblocks = (seg_reads + 63) / 64, need = (nblocks + STREAM_NW_HOST - 1) / STREAM_NW_HOST;
       if (need < wgrid) wgrid = (unsigned)(need ? need : 1);
    }
-   const size_t hit_blocks = (s->cap_hitlines + WG - 1) / WG;
-   unsigned grid_hits = (unsigned)(hit_blocks < (size_t)s->ncu * 16 ? hit_blocks : (size_t)s->ncu * 16);
-   if (grid_hits == 0) grid_hits = 1;
+   const unsigned grid_hits = capped_grid(s, s->cap_hitlines, 16);
    const size_t nseg = (size_t)((b.nreads + PACKED_SEG_READS - 1) / PACKED_SEG_READS);
-   s->prof_segs = 0;
-   if (s->prof && nseg > s->nev_seg) {
-      hipEvent_t *g = (hipEvent_t *)realloc(s->ev, 4 * nseg * sizeof(hipEvent_t));
-      if (!g) { seeqerr = 0; errno = ENOMEM; return -1; }
-      s->ev = g;
-      for (size_t i = 4 * s->nev_seg; i < 4 * nseg; i++) HIP_TRY(hipEventCreate(&s->ev[i]), EIO);
-      s->nev_seg = nseg;
-   }
-   if (s->prof) s->prof_segs = nseg;
+   if (prof_events(s, nseg)) return -1;
    for (size_t sg = 0; sg < nseg; sg++) {
       hipEvent_t *ev = s->prof ? s->ev + 4 * sg : NULL;
       PackedArgs p;
@@ -1901,15 +1839,12 @@ static int run_packed(seeqdev_scan *s)
       const uint32_t *eqp = (const uint32_t *)s->d_eqtab;
       const uint32_t *hcol = s->hit_col;
       uint4 *ecache = want == SEEQDEV_WANT_RECORDS ? s->ow.tmp : nullptr;
-      const int seg_flags = 1 | (!nh_is_count ? 2 : 0);
       {
          /* the exact pass of the candidates: k_verify_packed on the batch itself, or (SQ_ALL records) k_verify over the staging text -- ASCII lines,
             no byte of them is skipped (seeq_verify.h) */
-         const bool count_any = want != SEEQDEV_WANT_COUNTMATCH && !(want == SEEQDEV_WANT_RECORDS && match_opt == SQ_ALL);
-         const int var = (want == SEEQDEV_WANT_RECORDS && match_opt == SQ_BEST) ? VERIFY_BEST : count_any ? VERIFY_ANY : VERIFY_ALL;
+         const int var = verify_variant(want, options, nh_is_count, seg_flags, &a.fin);
          a.nh_sum = s->nh_sum;
          a.nz_sum = nh_is_count ? s->nh_sum + (s->cap_hitlines / 256 + 2) : nullptr;
-         a.fin = (want == SEEQDEV_WANT_RECORDS && var == VERIFY_ALL) ? 0u : 1u + (uint32_t)seg_flags;
          if (direct) seeq_launch_verify_packed(fw, var, grid_hits, st, a, b.bases, b.nmask, b.stride, b.nstride, L, p.total_bytes,
                                                b.nmask ? b.nreads * (uint64_t)b.nstride : 0ull, eqp, hcol, ecache);
          else seeq_launch_verify(fw, var, grid_hits, st, a, eqp, hcol, ecache);
@@ -1970,13 +1905,12 @@ static int multi_ws_ensure(seeqdev_scan *s, int npat)
 }
 
 /* The part of a segment behind the union walk: `ua` = the union scan's arguments (hit list made, bounds done). */
-static int multi_post(seeqdev_scan *s, const ScanArgs &ua, hipStream_t st)
+static int multi_post(seeqdev_scan *s, const ScanPlan &plan, const ScanArgs &ua, hipStream_t st)
 {
    const MultiPlan *mp = s->mplan;
    const int npat = mp->npat;
    const int options = s->options, want = s->want;
    const int match_opt = options & 3;
-   const bool nh_is_count = want == SEEQDEV_WANT_COUNTMATCH || (want == SEEQDEV_WANT_RECORDS && match_opt == SQ_ALL);
    const uint32_t capP = (uint32_t)(s->cap_hitlines / (size_t)npat);
    const uint64_t capR = s->cap_records / (uint64_t)npat;
    MultiArgs m;
@@ -2021,9 +1955,7 @@ static int multi_post(seeqdev_scan *s, const ScanArgs &ua, hipStream_t st)
    }
    /* The exact pass, every pattern in one launch per step (blockIdx.y = pattern; one-word patterns first, then the two-word
       ones): the patterns' arguments go to HBM through a page-locked ring, one slot per segment. */
-   const size_t hit_blocks = ((size_t)capP + WG - 1) / WG;
-   unsigned grid_hits = (unsigned)(hit_blocks < (size_t)s->ncu * 4 ? hit_blocks : (size_t)s->ncu * 4);      /* (x npat workgroups per launch) */
-   if (grid_hits == 0) grid_hits = 1;
+   const unsigned grid_hits = capped_grid(s, capP, 4);      /* (x npat workgroups per launch) */
    if (s->mx_next == s->mx_slots) { HIP_TRY(hipStreamSynchronize(st), EIO); s->mx_next = 0; }
    MultiExact *hx = s->h_mx + s->mx_next * SEEQ_MULTI_MAX, *dx = s->d_mx + s->mx_next * SEEQ_MULTI_MAX;
    s->mx_next++;
@@ -2052,13 +1984,13 @@ static int multi_post(seeqdev_scan *s, const ScanArgs &ua, hipStream_t st)
       x.cache = want == SEEQDEV_WANT_RECORDS ? s->ow.tmp + (size_t)k * capP : nullptr;
       x.scan_ws = s->m_scan_ws + (size_t)k * nbp;
       x.nb = nbp;
-      x.seg_end_flags = 1 | (!nh_is_count ? 2 : 0);
+      x.seg_end_flags = seg_end_flags(plan.need_nh, plan.superset, plan.nh_is_count);
    }
    HIP_TRY(hipMemcpyAsync(dx, hx, (size_t)npat * sizeof(MultiExact), hipMemcpyHostToDevice, st), EIO);
    const int mo = match_opt == SQ_COUNT ? SQ_FIRST : match_opt;
    if (n1) hipLaunchKernelGGL((k_exact1m<SQ_MODE_COUNT, 1, -1>), dim3(grid_hits, (unsigned)n1), dim3(WG), 0, st, (const MultiExact *)dx);
    if (n2) hipLaunchKernelGGL((k_exact1m<SQ_MODE_COUNT, 2, -1>), dim3(grid_hits, (unsigned)n2), dim3(WG), 0, st, (const MultiExact *)(dx + n1));
-   if (nh_is_count) hipLaunchKernelGGL(k_multi_count_nonzero, dim3(grid_hits < 128 ? grid_hits : 128, (unsigned)npat), dim3(WG), 0, st, (const MultiExact *)dx);
+   if (plan.nh_is_count) hipLaunchKernelGGL(k_multi_count_nonzero, dim3(grid_hits < 128 ? grid_hits : 128, (unsigned)npat), dim3(WG), 0, st, (const MultiExact *)dx);
    hipLaunchKernelGGL(k_multi_scan_reduce, dim3(nbp, (unsigned)npat), dim3(WG), 0, st, (const MultiExact *)dx);
    hipLaunchKernelGGL(k_multi_scan_top, dim3((unsigned)npat), dim3(WG), 0, st, (const MultiExact *)dx, want == SEEQDEV_WANT_RECORDS ? 1 : 0);
    hipLaunchKernelGGL(k_multi_scan_apply, dim3(nbp, (unsigned)npat), dim3(WG), 0, st, (const MultiExact *)dx);
@@ -2144,14 +2076,17 @@ static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const voi
          foreign += b != '\n' && sq_class_of(b, 0) >= 5;
       }
       s->avg_line = nl ? (double)n / (double)nl : 1e9;
-      /* more than one foreign byte per 4 KB (FASTQ: every quality line): nearly every 8 KB tile of k_pair would take its slow
-         path (exact alphabet check over the text fetched again) -- k_stream walks such text at full speed */
+      /* more than one foreign byte per 4 KB (FASTQ: every quality line; FASTA: a header per read): FASTA input of that kind stays
+         with k_stream, FASTQ with k_pair (seeq_plan.h) */
       s->sample_dirty = foreign * 4096 > n;
       s->avg_text = d_text;
       s->avg_nbytes = nbytes;
    }
    return 0;
 }
+
+/* The capacity a re-run asks for where a workspace overflowed: what the device reported it needs, plus an eighth */
+static size_t grown(uint64_t need) { return (size_t)need + (size_t)(need >> 3) + 64; }
 
 extern "C" int seeqdevScanFetch(seeqdev_scan_t *s, seeqdev_counts_t *counts)
 {
@@ -2201,24 +2136,21 @@ extern "C" int seeqdevScanFetch(seeqdev_scan_t *s, seeqdev_counts_t *counts)
       }
       /* Grow to what the device reported (plus slack for the parts it could not see) and re-run. */
       size_t nl = s->cap_lines, nhl = s->cap_hitlines, nrec = s->cap_records;
-      if (h.overflow & 1u) nl = (size_t)h.need_lines + (h.need_lines >> 3) + 64;
-      if (h.overflow & 2u) nhl = (size_t)h.need_hitlines + (h.need_hitlines >> 3) + 64;
-      if (h.overflow & 64u) {
+      if (h.overflow & OVF_LINES) nl = grown(h.need_lines);
+      if (h.overflow & OVF_HITLINES) nhl = grown(h.need_hitlines);
+      if (h.overflow & OVF_BAD_ENTRY) {
          snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the hit list (k_stream_bounds)");
          errno = EIO;
          return -1;
       }
-      if (h.overflow & 8u) s->no_stream = true;
-      if (h.overflow & 16u) s->no_stream_nd = true;
-      if (h.overflow & 32u) s->force_ll = true;
-      if (h.overflow & 128u) s->no_window = true;            /* a line with candidates on both sides of a segment seam */
-      if (h.overflow & 256u) s->no_leaders = true;           /* a leader's fresh start inside the walk before it */
-      if (h.overflow & (8u | 16u | 32u | 128u | 256u)) s->fallback_ttl = 32;
-      if (h.overflow & 4u) {
-         /* need_records keeps counting after the overflow, so it is the total of this run. */
-         nrec = (size_t)h.need_records + (size_t)(h.need_records >> 3) + 64;
-      }
-      if ((h.overflow & 1u) && nhl < nl / 8) nhl = nl / 8 + 64;
+      if (h.overflow & OVF_NO_STREAM) s->no_stream = true;
+      if (h.overflow & OVF_NONDNA) s->no_stream_nd = true;
+      if (h.overflow & OVF_LONG_LINES) s->force_ll = true;
+      if (h.overflow & OVF_SEAM) s->no_window = true;        /* a line with candidates on both sides of a segment seam */
+      if (h.overflow & OVF_LEADER) s->no_leaders = true;     /* a leader's fresh start inside the walk before it */
+      if (h.overflow & OVF_FALLBACK) s->fallback_ttl = 32;
+      if (h.overflow & OVF_RECORDS) nrec = grown(h.need_records);     /* (need_records keeps counting after the overflow: the total of this run) */
+      if ((h.overflow & OVF_LINES) && nhl < nl / 8) nhl = nl / 8 + 64;
       if (attempt == 7) break;
       if (reserve_impl(s, s->nbytes, nl, nhl, nrec)) return -1;
       if (dispatch_run(s)) return -1;
@@ -2353,6 +2285,14 @@ extern "C" void seeqdevHostFree(void *p)
    if (p) (void)hipHostFree(p);
 }
 
+/* A context borrowed for scans of patterns it does not own: nothing of them is left to fetch, re-run or copy */
+static void scan_forget(seeqdev_scan *s)
+{
+   s->pat = nullptr;
+   s->ran = false;
+   memset(&s->counts, 0, sizeof s->counts);
+}
+
 /* Device memory for RESIDENT TEXT, chosen by measurement.  The scan kernel's time follows the physical pages a buffer gets from the driver
  * (0.77 / 0.87 / 0.92 ms per 3.75 GiB for the same text, stable for the life of the allocation; power-of-two blocks are fast far more often
  * than requests of an odd size: DESIGN.md section 5 (i)-(l)), so a caller that keeps text resident chooses its buffer once: up to twelve
@@ -2400,7 +2340,8 @@ extern "C" void *seeqdevTextAllocFor(seeqdev_scan_t *scan, size_t bytes, int can
       seeqdev_pattern_t *pat = seeqdevPatternNew(keys, 20, 3);
       /* Round 5: the launch time is a property of the PAIR (text buffer, scan context's workspace) -- the same text runs at 0.72 or 0.84 ms with
          two contexts of one process, reproducibly (profiles/r05/workspace_probe.txt) -- so a caller that scans the text with a context of its own
-         (`scan`: reserve it first, so that its workspace is the one that stays) has the candidates probed with THAT context; NULL: a context made here. */
+         (`scan`: reserve it first, so that its workspace is the one that stays) has the candidates probed with THAT context, and is left with no scan to fetch;
+         NULL: a context made here. */
       sc = pat ? (scan ? scan : seeqdevScanNew(NULL)) : NULL;
       const bool own_sc = scan == nullptr;
       const bool prof_was = sc ? sc->prof : false;
@@ -2417,7 +2358,7 @@ extern "C" void *seeqdevTextAllocFor(seeqdev_scan_t *scan, size_t bytes, int can
          ms[i] = t[1];
       }
       if (sc && own_sc) seeqdevScanFree(sc);
-      else if (sc) (void)seeqdevScanSetProfiling(sc, prof_was ? 1 : 0);
+      else if (sc) { (void)seeqdevScanSetProfiling(sc, prof_was ? 1 : 0); scan_forget(sc); }
       if (pat) seeqdevPatternFree(pat);
       if (ok) {
          for (int i = 1; i < n; i++) if (ms[i] < ms[best]) best = i;
@@ -2458,25 +2399,34 @@ extern "C" int seeqdevScanCopyOffsets(seeqdev_scan_t *s, uint64_t *host_out, siz
    return 0;
 }
 
+/* Host text into the context's staging buffer, on its stream (timed: between the H2D events).  New contents behind the same pointer:
+   the line length is sampled again */
+static int text_upload(seeqdev_scan *s, const char *host_text, size_t nbytes, bool timed)
+{
+   if (nbytes > s->cap_text) {
+      const size_t cap = nbytes + (nbytes >> 2) + 4096;
+      if (ws_alloc((void **)&s->d_text, cap)) return -1;
+      s->cap_text = cap;
+   }
+   if (timed) HIP_TRY(hipEventRecord(s->ev_h2d[0], s->stream), EIO);
+   if (nbytes) HIP_TRY(hipMemcpyAsync(s->d_text, host_text, nbytes, hipMemcpyHostToDevice, s->stream), EIO);
+   if (timed) HIP_TRY(hipEventRecord(s->ev_h2d[1], s->stream), EIO);
+   s->avg_text = NULL;
+   return 0;
+}
+
 extern "C" int seeqdevScanHostBegin(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const char *host_text, size_t nbytes,
                                     int options, int want)
 {
    seeqerr = 0;
    if (!s || !pat || (!host_text && nbytes)) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
-   if (nbytes > s->cap_text) {
-      const size_t cap = nbytes + (nbytes >> 2) + 4096;
-      if (ws_alloc((void **)&s->d_text, cap)) return -1;
-      s->cap_text = cap;
-   }
    if (s->prof && !s->have_h2d_ev) {
       HIP_TRY(hipEventCreate(&s->ev_h2d[0]), EIO);
       HIP_TRY(hipEventCreate(&s->ev_h2d[1]), EIO);
       s->have_h2d_ev = true;
    }
-   if (s->prof) HIP_TRY(hipEventRecord(s->ev_h2d[0], s->stream), EIO);
-   if (nbytes) HIP_TRY(hipMemcpyAsync(s->d_text, host_text, nbytes, hipMemcpyHostToDevice, s->stream), EIO);
-   if (s->prof) HIP_TRY(hipEventRecord(s->ev_h2d[1], s->stream), EIO);
+   if (text_upload(s, host_text, nbytes, s->prof)) return -1;
    /* the line-length sample (kernel selection) comes from the host copy: no round trip, nothing stale */
    if (s->line_hint <= 0 && !(options & SEEQDEV_SINGLELINE) && nbytes) {
       const size_t n = nbytes < SAMPLE_BYTES ? nbytes : SAMPLE_BYTES;
@@ -2485,8 +2435,6 @@ extern "C" int seeqdevScanHostBegin(seeqdev_scan_t *s, const seeqdev_pattern_t *
       s->avg_line = nl ? (double)n / (double)nl : 1e9;
       s->avg_text = s->d_text;
       s->avg_nbytes = nbytes;
-   } else {
-      s->avg_text = NULL;
    }
    return seeqdevScanRun(s, pat, s->d_text, nbytes, options, want);
 }
@@ -2543,26 +2491,7 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
    if (mp->eq_options != options) {
       uint32_t *h = (uint32_t *)calloc((size_t)npat * 1536, sizeof(uint32_t));
       if (!h) { errno = ENOMEM; return -1; }
-      for (int k = 0; k < npat; k++) {
-         const seeqdev_pattern *pat = pats[k];
-         const int Wp = pat->words, fw = mp->fw[k];
-         uint32_t *tab = h + (size_t)k * 1536;
-         for (int dir = 0; dir < 2; dir++)
-            for (int b = 0; b < 256; b++) {
-               const uint8_t cls = sq_class_of((uint32_t)b, options);
-               uint64_t v;
-               if (cls < 5) {
-                  const uint32_t *q = pat->h_peq + (dir * 5 + cls) * Wp;
-                  const uint64_t col = (uint64_t)q[0] | (Wp > 1 ? (uint64_t)q[1] << 32 : 0);
-                  v = col << (32 * fw - pat->wlen);
-               } else {
-                  v = cls == SQC_TERM ? FUSED_FLAG_TERM : FUSED_FLAG_SKIP;
-               }
-               uint32_t *dst = tab + (size_t)(dir * 256 + b) * fw;
-               dst[0] = (uint32_t)v;
-               if (fw == 2) dst[1] = (uint32_t)(v >> 32);
-            }
-      }
+      for (int k = 0; k < npat; k++) eq_fill(h + (size_t)k * 1536, pats[k], options, mp->fw[k]);
       const hipError_t e = hipMemcpy(mp->d_eq, h, (size_t)npat * 1536 * sizeof(uint32_t), hipMemcpyHostToDevice);
       free(h);
       if (e != hipSuccess) return hip_fail(e, "hipMemcpy(EQ tables)", EIO);
@@ -2587,8 +2516,8 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
          if (s->h_mcnt[k].need_hitlines > need_hl) need_hl = s->h_mcnt[k].need_hitlines;
          if (s->h_mcnt[k].need_records > need_rec) need_rec = s->h_mcnt[k].need_records;
       }
-      if (u.overflow & 64u) { snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the hit list (k_stream_bounds)"); errno = EIO; break; }
-      if (u.overflow & (8u | 16u | 32u)) { rc = 1; break; }          /* not k_pair's text after all: a scan per pattern */
+      if (u.overflow & OVF_BAD_ENTRY) { snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the hit list (k_stream_bounds)"); errno = EIO; break; }
+      if (u.overflow & (OVF_NO_STREAM | OVF_NONDNA | OVF_LONG_LINES)) { rc = 1; break; }          /* not k_pair's text after all: a scan per pattern */
       if (!u.overflow && !povf) {
          /* results: counts, then every pattern's records from its region */
          const uint64_t capR = s->cap_records / (uint64_t)npat;
@@ -2622,12 +2551,12 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
          break;
       }
       size_t nl = s->cap_lines, nhl = s->cap_hitlines, nrec = s->cap_records;
-      if (u.overflow & 1u) nl = (size_t)u.need_lines + (u.need_lines >> 3) + 64;
-      if (u.overflow & 2u) nhl = (size_t)u.need_hitlines + (u.need_hitlines >> 3) + 64;
-      if (u.overflow & 128u) { s->no_window = true; s->fallback_ttl = 32; }
-      if (povf & 2u) { const size_t w = ((size_t)need_hl + (need_hl >> 3) + 64) * (size_t)npat; if (w > nhl) nhl = w; }
-      if (povf & 4u) { const size_t w = ((size_t)need_rec + (size_t)(need_rec >> 3) + 64) * (size_t)npat; if (w > nrec) nrec = w; }
-      if ((u.overflow & 1u) && nhl < nl / 2) nhl = nl / 2 + 64;
+      if (u.overflow & OVF_LINES) nl = grown(u.need_lines);
+      if (u.overflow & OVF_HITLINES) nhl = grown(u.need_hitlines);
+      if (u.overflow & OVF_SEAM) { s->no_window = true; s->fallback_ttl = 32; }
+      if (povf & OVF_HITLINES) { const size_t w = grown(need_hl) * (size_t)npat; if (w > nhl) nhl = w; }
+      if (povf & OVF_RECORDS) { const size_t w = grown(need_rec) * (size_t)npat; if (w > nrec) nrec = w; }
+      if ((u.overflow & OVF_LINES) && nhl < nl / 2) nhl = nl / 2 + 64;
       if (attempt == 7) { snprintf(g_last_error, sizeof g_last_error, "workspace did not converge"); errno = ENOMEM; break; }
       if (reserve_impl(s, s->nbytes, nl, nhl, nrec)) break;
    }
@@ -2683,13 +2612,7 @@ extern "C" int seeqdevScanHostMulti(seeqdev_scan_t *s, const seeqdev_pattern_t *
    seeqerr = 0;
    if (!s || !pats || npat < 1 || (!host_text && nbytes)) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
-   if (nbytes > s->cap_text) {
-      const size_t cap = nbytes + (nbytes >> 2) + 4096;
-      if (ws_alloc((void **)&s->d_text, cap)) return -1;
-      s->cap_text = cap;
-   }
-   if (nbytes) HIP_TRY(hipMemcpyAsync(s->d_text, host_text, nbytes, hipMemcpyHostToDevice, s->stream), EIO);   /* once, for all patterns */
-   s->avg_text = NULL;                                     /* new contents behind the same pointer: sample again */
+   if (text_upload(s, host_text, nbytes, false)) return -1;      /* once, for all patterns */
    return seeqdevScanRunMulti(s, pats, npat, s->d_text, nbytes, options, want, counts);
 }
 
@@ -2881,10 +2804,7 @@ extern "C" int seeqdevScanRunDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *c
    s->last_multi = 0;
    int rc = multi_one_pass(s, pats, npat, d_text, nbytes, opts, SEEQDEV_WANT_RECORDS, nullptr, true);
    if (rc == 1) rc = demux_per_pattern(s, pats, npat, d_text, nbytes, opts);
-   /* the borrowed context: nothing of these scans is left to fetch, re-run or copy (their patterns are the caller's) */
-   s->pat = nullptr;
-   s->ran = false;
-   memset(&s->counts, 0, sizeof s->counts);
+   scan_forget(s);                                         /* (the patterns are the caller's) */
    if (rc) { s->dm_nrec = 0; return -1; }
    const DemuxCnt &h = *s->h_dmcnt;
    sum->nlines = s->dm_nlines;
@@ -2900,13 +2820,7 @@ extern "C" int seeqdevScanHostDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *
    seeqerr = 0;
    if (!demux_args_ok(s, pats, npat, host_text, nbytes, options, sum)) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
-   if (nbytes > s->cap_text) {
-      const size_t cap = nbytes + (nbytes >> 2) + 4096;
-      if (ws_alloc((void **)&s->d_text, cap)) return -1;
-      s->cap_text = cap;
-   }
-   if (nbytes) HIP_TRY(hipMemcpyAsync(s->d_text, host_text, nbytes, hipMemcpyHostToDevice, s->stream), EIO);
-   s->avg_text = NULL;                                     /* new contents behind the same pointer: sample again */
+   if (text_upload(s, host_text, nbytes, false)) return -1;
    return seeqdevScanRunDemux(s, pats, npat, s->d_text, nbytes, options, sum, per_pattern);
 }
 

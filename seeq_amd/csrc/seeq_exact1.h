@@ -156,7 +156,7 @@ __device__ __forceinline__ void exact1_body(const ScanArgs &a, const uint32_t *e
    const Counters *c = a.cnt;
    const uint32_t nhl = c->seg_nhitlines;
    const int match_opt = OPT >= 0 ? OPT : (a.options & 3);
-   if (MODE == SQ_MODE_EMIT && (c->overflow & 4u)) return;
+   if (MODE == SQ_MODE_EMIT && (c->overflow & OVF_RECORDS)) return;
    const uint32_t m = (uint32_t)a.m, tau1 = (uint32_t)a.tau + 1;
    const bool count_any = a.want != SEEQDEV_WANT_COUNTMATCH && !(a.want == SEEQDEV_WANT_RECORDS && match_opt == SQ_ALL);
    const bool by_nh = a.use_nh != 0;                       /* record slots come from the scanned per-line counts */

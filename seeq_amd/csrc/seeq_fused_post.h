@@ -12,7 +12,7 @@ __global__ __launch_bounds__(256) void k_fused_post(FusedArgs a, uint32_t nslice
 __global__ __launch_bounds__(256) void k_fused_reorder(FusedArgs a, uint32_t nslices, uint32_t *hit_start, uint32_t *hit_line)
 {
    const Counters *c = a.cnt;
-   if (c->overflow & 2u) return;
+   if (c->overflow & OVF_HITLINES) return;
    const uint32_t lane = threadIdx.x & 63;
    for (uint32_t sl = blockIdx.x * 4 + (threadIdx.x >> 6); sl < nslices; sl += gridDim.x * 4) {      /* one wave per slice */
       const uint32_t n = a.wg_hits[sl];

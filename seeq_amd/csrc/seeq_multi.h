@@ -89,7 +89,7 @@ __global__ __launch_bounds__(MULTI_RESOLVE_WG) void k_multi_resolve(MultiArgs a)
       if (repeat) {
          if (whole) continue;                              /* the first entry's lane walks the whole line */
          while (f > 0 && hs == 0xFFFFFFFFu) hs = a.hit_start[--f];
-         if (hs == 0xFFFFFFFFu) continue;                  /* the line's first candidate belongs to the segment before this one (the run is void: overflow 128) */
+         if (hs == 0xFFFFFFFFu) continue;                  /* the line's first candidate belongs to the segment before this one (the run is void: OVF_SEAM) */
       }
       const uint32_t c = repeat ? a.hit_col[k] - hs : a.hit_col[k];
       const uint64_t off = a.seg_base + hs;
@@ -190,8 +190,8 @@ __global__ __launch_bounds__(256) void k_multi_top(MultiArgs a)
       const Counters *u = a.ucnt;
       uint32_t n = running;
       if (!a.trust && n > pc->need_hitlines) pc->need_hitlines = n;
-      if (!a.trust && n > a.capP) { pc->overflow |= 2u; n = 0; }
-      if (pc->overflow & 2u) n = 0;
+      if (!a.trust && n > a.capP) { pc->overflow |= OVF_HITLINES; n = 0; }
+      if (pc->overflow & OVF_HITLINES) n = 0;
       pc->seg_nhitlines = n;
       pc->seg_nlines = u->seg_nlines;
       pc->seg_nheaders = u->seg_nheaders;
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void k_multi_apply(MultiArgs a)
    if (lane < a.npat) {
       mybase = a.bsum[lane * a.nb + blockIdx.x];
       for (uint32_t w = 0; w < wave; w++) mybase += s_cnt[w][lane];
-      room = !(a.pcnt[lane].overflow & 2u);                /* the region is too small: the scan is run again */
+      room = !(a.pcnt[lane].overflow & OVF_HITLINES);      /* the region is too small: the scan is run again */
    }
    for (int r = 0; r < MULTI_ITEMS; r++) {
       const uint32_t i = wbase + (uint32_t)r * 64u + lane;

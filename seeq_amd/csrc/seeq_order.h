@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void k_order(FusedArgs f, uint32_t nslices, co
    __shared__ uint32_t s_ph[ORDER_MAX_BLOCKS], s_pc[ORDER_MAX_BLOCKS], s_wave[4];
    order_block_prefix(bsum, nb, s_ph, s_pc, s_wave);
    const Counters *c = f.cnt;
-   if (c->overflow & 2u) return;
+   if (c->overflow & OVF_HITLINES) return;
    const uint32_t lane = threadIdx.x & 63;
    const uint32_t lines0 = (uint32_t)c->lines;
    for (uint32_t sl = blockIdx.x * 4 + (threadIdx.x >> 6); sl < nslices; sl += gridDim.x * 4) {      /* one wave per slice */
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void k_bounds2(ScanArgs a, uint4 *ent, uint32_
                const uint64_t hp0 = a.seg_base + e.x;
                voids = hp0 < a.nbytes && order_marker_holds(a, order_line_start(a.text, hp0));
             }
-            if (voids) atomicOr(&c->overflow, 128u);
+            if (voids) atomicOr(&c->overflow, OVF_SEAM);
          }
          a.hit_start[k] = 0xFFFFFFFFu;
          continue;
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) void k_bounds2(ScanArgs a, uint4 *ent, uint32_
       }
       const uint64_t hp = a.seg_base + e.x;               /* a byte of the line (inside the segment); never '\n' */
       if (hp >= a.nbytes || hp < segb || hp >= segb + a.seg_len) {       /* cannot be: an entry the scan kernel never wrote -- fail loudly, touch nothing */
-         atomicOr(&c->overflow, 64u);
+         atomicOr(&c->overflow, OVF_BAD_ENTRY);
          a.hit_start[k] = 0xFFFFFFFFu;
          hit_col[k] = 0u;
          continue;
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void k_bounds2(ScanArgs a, uint4 *ent, uint32_
          ent[k].w = e.w | 4u;                             /* (bit 2: a marker no more) */
       }
       uint32_t out_start, out_col;
-      if (q < a.seg_base) { atomicOr(&c->overflow, 8u); out_start = 0xFFFFFFFFu; out_col = 0u; }
+      if (q < a.seg_base) { atomicOr(&c->overflow, OVF_NO_STREAM); out_start = 0xFFFFFFFFu; out_col = 0u; }
       else if (!keep) { out_start = 0xFFFFFFFFu; out_col = 0u; }
       else { out_start = (uint32_t)(q - a.seg_base); out_col = (uint32_t)(hp - q); }
       a.hit_start[k] = out_start;

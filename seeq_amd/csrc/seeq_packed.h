@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64 * STREAM_NW, 8) void k_packed_walk(PackedArgs a)
    }
    packed_stage_store(a, pend, (uint32_t)lane & 15u);
    if (wave_over && lane == 0) {                           /* the wave's share of the staging text is too small: the scan is run again with more */
-      atomicOr(&a.cnt->overflow, 2u);
+      atomicOr(&a.cnt->overflow, OVF_HITLINES);
       atomicMax(&a.cnt->need_hitlines, wslots * nwaves);
    }
 }
@@ -292,8 +292,8 @@ __global__ void k_packed_counts(PackedArgs a)
    Counters *c = a.cnt;
    uint32_t n = c->seg_nhitlines;                          /* total of the flag scan */
    if (n > c->need_hitlines) c->need_hitlines = n;
-   if (n > a.cap) { atomicOr(&c->overflow, 2u); n = 0; }
-   if (c->overflow & 2u) n = 0;
+   if (n > a.cap) { atomicOr(&c->overflow, OVF_HITLINES); n = 0; }
+   if (c->overflow & OVF_HITLINES) n = 0;
    c->seg_nhitlines = n;
    c->seg_nrec = n;
    c->seg_nlines = a.nreads;

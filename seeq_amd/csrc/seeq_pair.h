@@ -40,7 +40,7 @@
  *
  * Everything k_pair reports is a CANDIDATE (ScanArgs.filter): the exact pass (k_exact1) verifies each one -- under
  * SQ_FAIL and SQ_CONVERT alike, since aliasing is harmless for a superset (SQ_IGNORE, where a skipped byte stretches a
- * match, stays with k_stream).  The alphabet check and Counters.dirty are kept: when the text holds a byte that could
+ * match, adds line markers: IG below).  The alphabet check and Counters.dirty are kept: when the text holds a byte that could
  * end a line early, the exact pass looks at the bytes between the line's start and a candidate's window before it trusts
  * the window (verify_prefix_dirty, seeq_verify.h).
  * Bookkeeping (newline masks, line ranks, line starts, slices, FASTA headers) is k_stream's.

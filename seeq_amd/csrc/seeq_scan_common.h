@@ -208,7 +208,7 @@ __device__ __forceinline__ void rec_check_body(const ScanArgs &a)
 {
    Counters *c = a.cnt;
    c->need_records = c->records + c->seg_nrec;     /* running total incl. this segment */
-   if (c->records + c->seg_nrec > a.cap_records) atomicOr(&c->overflow, 4u);
+   if (c->records + c->seg_nrec > a.cap_records) atomicOr(&c->overflow, OVF_RECORDS);
 }
 
 __device__ __forceinline__ void seg_end_body(const ScanArgs &a, int flags /* 1: hits come from nh[]; 2: nh[] holds 0/1 verdicts, their sum = matching lines */)
@@ -303,7 +303,7 @@ __device__ __forceinline__ void fused_post_body(const FusedArgs &a, uint32_t nsl
       flags = s_flags[0] | s_flags[1] | s_flags[2] | s_flags[3];
       if (flags & 1u) {
          c->dirty |= 1u;
-         if ((a.options & MASK_NONDNA) && !a.pair) c->overflow |= 16u;     /* SQ_CONVERT / SQ_IGNORE: k_stream is only exact on clean text -> re-run (k_pair's candidates are verified anyway) */
+         if ((a.options & MASK_NONDNA) && !a.pair) c->overflow |= OVF_NONDNA;     /* SQ_CONVERT / SQ_IGNORE: k_stream is only exact on clean text -> re-run (k_pair's candidates are verified anyway) */
       }
       if (flags & 4u) {
          c->dirty |= 1u;                                      /* skip bytes in a warm-up window / a NUL: the hit lines are candidates */
@@ -312,19 +312,19 @@ __device__ __forceinline__ void fused_post_body(const FusedArgs &a, uint32_t nsl
             waves: more than half of those that saw text made up more candidates than a quarter of their lines.) */
          busy = s_busy[0] + s_busy[1] + s_busy[2] + s_busy[3];
          crowded = s_crowded[0] + s_crowded[1] + s_crowded[2] + s_crowded[3];
-         if ((a.options & MASK_NONDNA) == SQ_IGNORE && crowded * 2 > busy) c->overflow |= 16u;
+         if ((a.options & MASK_NONDNA) == SQ_IGNORE && crowded * 2 > busy) c->overflow |= OVF_NONDNA;
       }
-      if (flags & 2u) c->overflow |= 32u;                     /* re-run once with the long-line variant (then kept) */
+      if (flags & 2u) c->overflow |= OVF_LONG_LINES;          /* re-run once with the long-line variant (then kept) */
       c->seg_nlines = lines;
       c->seg_nheaders = hdrs;
       /* capacity wanted next time: every slice as large as the fullest one, plus slack */
       const uint64_t need = (uint64_t)mx * nslices + (uint64_t)nslices * 64;
       if (need > c->need_hitlines) c->need_hitlines = need > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)need;
-      if (ovf) { atomicOr(&c->overflow, 2u); hits = 0; }
+      if (ovf) { atomicOr(&c->overflow, OVF_HITLINES); hits = 0; }
       /* a hit list overflowed, in this segment or in an earlier one: the run is void (seeqdevScanFetch grows the workspace
          and runs it again) and k_stream_reorder / k_fused_reorder write nothing any more -- so no later kernel of this
          run may look at the (stale) hit arrays either: no hit lines from here on */
-      if (c->overflow & 2u) hits = 0;
+      if (c->overflow & OVF_HITLINES) hits = 0;
       c->seg_nhitlines = hits;
       c->seg_nrec = hits;                                   /* (k_seg_mid's job; the slices cannot hold more than cap_hitlines) */
       if (hits > c->need_hitlines) c->need_hitlines = hits;

@@ -648,7 +648,7 @@ __global__ __launch_bounds__(256) void k_stream_reorder(FusedArgs a, uint32_t ns
                                                         uint32_t *unresolved, uint32_t *hit_col)
 {
    const Counters *c = a.cnt;
-   if (c->overflow & 2u) return;
+   if (c->overflow & OVF_HITLINES) return;
    const uint32_t lane = threadIdx.x & 63;
    for (uint32_t sl = blockIdx.x * 4 + (threadIdx.x >> 6); sl < nslices; sl += gridDim.x * 4) {      /* one wave per slice */
       const uint32_t n = a.wg_hits[sl];
@@ -736,14 +736,14 @@ __global__ __launch_bounds__(256) void k_stream_bounds(ScanArgs a, uint32_t *hit
          hit_col[k] = (a.nh[k] & 1u) ? a.hit_start[k] : a.hit_start[k] + hit_col[k];
          /* k_pair, windows: the line's first candidate belongs to the segment before this one, whose exact pass could not
             know of this one -- the run is void, the next one scans candidate lines to their ends (seeqdevScanFetch) */
-         if (a.window_ok && ln == c->prev_hit_line) atomicOr(&c->overflow, 128u);
+         if (a.window_ok && ln == c->prev_hit_line) atomicOr(&c->overflow, OVF_SEAM);
          a.hit_start[k] = 0xFFFFFFFFu;
          continue;
       }
       if (!(a.nh[k] & 1u)) continue;                      /* k_stream already found the start of the line */
       const uint64_t hp = a.seg_base + a.hit_start[k];   /* a byte of the line (inside the segment); never '\n' */
       if (hp >= a.nbytes || hp < segb || hp >= segb + a.seg_len) {       /* cannot be: an entry the scan kernel never wrote -- fail loudly, touch nothing */
-         atomicOr(&c->overflow, 64u);
+         atomicOr(&c->overflow, OVF_BAD_ENTRY);
          a.hit_start[k] = 0xFFFFFFFFu;
          continue;
       }
@@ -778,7 +778,7 @@ __global__ __launch_bounds__(256) void k_stream_bounds(ScanArgs a, uint32_t *hit
          q = stream_line_start_in(a.text, 0, floor_ < hp ? floor_ : hp);
          if (q == ~(uint64_t)0) q = 0;
       }
-      if (q < a.seg_base) { atomicOr(&c->overflow, 8u); a.hit_start[k] = 0xFFFFFFFFu; }
+      if (q < a.seg_base) { atomicOr(&c->overflow, OVF_NO_STREAM); a.hit_start[k] = 0xFFFFFFFFu; }
       else {
          hit_col[k] = (uint32_t)(hp - q);
          a.hit_start[k] = (uint32_t)(q - a.seg_base);
@@ -955,7 +955,7 @@ __global__ __launch_bounds__(256) void k_lead_lines(ScanArgs a, const uint32_t *
 
 /* after COUNT: every leader's fresh start (wback columns before its candidate) must lie behind the end of the walk before
    it -- else that walk would have gone on into the leader's window (a score <= tau near the end of every chunk between them:
-   periodic patterns in periodic text) and the two lanes have counted the stretch twice: the run is void (overflow 256) */
+   periodic patterns in periodic text) and the two lanes have counted the stretch twice: the run is void (OVF_LEADER) */
 __global__ __launch_bounds__(256) void k_lead_check(ScanArgs a, const uint32_t *hit_col, const uint32_t *lflag, uint32_t wback)
 {
    const uint32_t nhl = a.cnt->seg_nhitlines;
@@ -964,7 +964,7 @@ __global__ __launch_bounds__(256) void k_lead_check(ScanArgs a, const uint32_t *
       if (lflag[k] != 2u) continue;
       const uint32_t abs_ = a.hit_start[k] + hit_col[k];
       /* (a walk that ran on to the end of its line never looked at this entry: the mark of k_lead_commit is still there) */
-      if (!((uint64_t)abs_ > (uint64_t)a.walk_end[k] + wback)) atomicOr(&a.cnt->overflow, 256u);
+      if (!((uint64_t)abs_ > (uint64_t)a.walk_end[k] + wback)) atomicOr(&a.cnt->overflow, OVF_LEADER);
    }
 }
 

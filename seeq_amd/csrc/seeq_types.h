@@ -11,6 +11,20 @@
 /* ========================================================================== */
 /* Device-side bookkeeping                                                    */
 /* ========================================================================== */
+/* Counters.overflow: why a run is void.  The first three ask seeqdevScanFetch for more workspace, the fall-back bits for other kernels. */
+enum : uint32_t {
+   OVF_LINES      = 1u,      /* per-line workspace too small */
+   OVF_HITLINES   = 2u,      /* hit-line workspace too small */
+   OVF_RECORDS    = 4u,      /* record workspace too small */
+   OVF_NO_STREAM  = 8u,      /* k_stream cannot serve this text: a hit line starts too far before its segment */
+   OVF_NONDNA     = 16u,     /* k_stream cannot serve this text: it holds bytes outside the alphabet */
+   OVF_LONG_LINES = 32u,     /* k_stream wants its long-line variant */
+   OVF_BAD_ENTRY  = 64u,     /* a hit entry points outside its segment (a bug: the scan fails) */
+   OVF_SEAM       = 128u,    /* k_pair: a line with candidates on both sides of a segment seam */
+   OVF_LEADER     = 256u,    /* long lines: a leader's fresh start lies inside the walk before it (the next run keeps a line in one lane) */
+   OVF_FALLBACK   = OVF_NO_STREAM | OVF_NONDNA | OVF_LONG_LINES | OVF_SEAM | OVF_LEADER,      /* the bits that set a context's fall-back flags */
+};
+
 struct Counters {
    /* per segment */
    uint32_t seg_nlines;     /* raw lines starting in the segment (FASTA headers included) */
@@ -24,7 +38,7 @@ struct Counters {
    uint64_t records;
    uint64_t headers;
    /* workspace overflow report */
-   uint32_t overflow;       /* 1 lines, 2 hit lines, 4 records (workspace too small); 8, 16: k_stream cannot serve this text; 32: wants its long-line variant; 64: a hit entry points outside its segment (a bug: the scan fails); 128: k_pair, a line with candidates on both sides of a seam; 256: long lines, a leader's fresh start lies inside the walk before it (the run is void, the next one keeps a line in one lane) */
+   uint32_t overflow;       /* OVF_* bits */
    uint32_t need_lines;     /* max over segments */
    uint32_t need_hitlines;  /* max over segments */
    uint32_t seg_novf;       /* k_exact1: 1 when a wave's overflow list (emissions beyond the first of their lines, COUNT -> EMIT) did not fit */

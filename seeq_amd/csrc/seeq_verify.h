@@ -492,7 +492,7 @@ __global__ __launch_bounds__(256) void k_nh_top(ScanArgs a)
 __global__ __launch_bounds__(256) void k_emit1(ScanArgs a, const uint4 *cache)
 {
    const Counters *c = a.cnt;
-   if (c->overflow & 4u) return;
+   if (c->overflow & OVF_RECORDS) return;
    const uint32_t nhl = c->emit_nhl;
    const uint64_t base = c->emit_base;
    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < nhl; k += gridDim.x * 256u) {
@@ -520,7 +520,7 @@ template <int W>
 __global__ __launch_bounds__(256, W == 1 ? 6 : 5) void k_emit_all(ScanArgs a, const uint32_t *eq2, const uint32_t *hit_col, uint4 *cache, uint32_t vgrid)
 {
    const Counters *c = a.cnt;
-   if (c->overflow & 4u) return;
+   if (c->overflow & OVF_RECORDS) return;
    if (c->seg_novf) { exact1_body<SQ_MODE_EMIT, W, -1, false>(a, eq2, hit_col, cache); return; }      /* (kernel-uniform) */
    __shared__ __align__(8) uint32_t s_eqr[256 * W];
    for (int i = threadIdx.x; i < 256 * W; i += 256) s_eqr[i] = eq2[256 * W + i];

@@ -346,6 +346,8 @@ def test_text_alloc_picks_a_buffer_by_measurement(gpu, capi):
     # text buffer / workspace -- which stays usable, profiling as it was, and scans the chosen buffer like any other
     sc.set_profiling(False)
     mine = dev.TextBuffer(nb, candidates=3, scanner=sc)
+    with pytest.raises(dev.SeeqDeviceError):
+        sc.fetch()                      # the probe's scans are not the caller's: nothing is left to fetch
     assert mine.ptr and len(mine.probe_ms) == 3 and all(t > 0 for t in mine.probe_ms) and mine.probe_ms[mine.chosen] == min(mine.probe_ms)
     dev.synth_reads(mine.ptr, 0, n, L, pattern, tau, stream=stream)
     torch.cuda.synchronize()
