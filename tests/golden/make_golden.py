@@ -9,6 +9,7 @@ reference produced for them.  Nothing of the reference's source is stored.
   ref_cli_cases.json    : reference CLI stdout for small input files
   reads_small.txt       : the shape-R / FASTQ-ish inputs those CLI cases use
   ref_fuzz_cases.json   : `make_golden.py fuzz` -- the reference's hits for the differential fuzz of test_oracle.py
+  ref_long_cases.json   : `make_golden.py long` -- the same for patterns of 63 .. 512 positions, distances up to 100
 """
 import hashlib
 import json
@@ -26,7 +27,10 @@ from oracle.pyoracle import (Reference, Oracle, REF_BIN, SQ_FIRST, SQ_BEST, SQ_A
 
 
 def rand_pattern(rng):
-    m = rng.choice([1, 2, 3, 4, 6, 8, 12, 16, 20, 20, 27, 31, 32, 33, 40, 48, 63, 64, 65, 70])
+    return pattern_of_length(rng, rng.choice([1, 2, 3, 4, 6, 8, 12, 16, 20, 20, 27, 31, 32, 33, 40, 48, 63, 64, 65, 70]))
+
+
+def pattern_of_length(rng, m):
     out = []
     for _ in range(m):
         x = rng.random()
@@ -118,6 +122,49 @@ def fuzz_cases(ref, rng, n):
     return cases
 
 
+LONG_M = (63, 64, 65, 71, 95, 96, 97, 127, 128, 129, 160, 255, 256, 257, 300, 384, 511, 512)
+LONG_TAU = (0, 1, 3, 8, 16, 31, 32, 33, 64, 100)
+
+
+def long_text(rng, pat, tau, L):
+    """rand_text at the lengths of long patterns: 0-3 planted copies with 0 .. tau + 2 edits, N and lower case per byte,
+    a foreign byte and a newline now and then -- per text, not per byte: one in a hundred bytes would end every line
+    before a pattern of hundreds of positions fits into it."""
+    text = ''.join(rng.choice('ACGT') for _ in range(L))
+    for _ in range(rng.randint(0, 3)):
+        cp = mutate(rng, plain(pat), rng.randint(0, tau + 2))
+        if text:
+            p = rng.randrange(len(text) + 1)
+            text = text[:p] + cp + text[p + len(cp):]
+    tl = list(text)
+    for i in range(len(tl)):
+        x = rng.random()
+        if x < 0.004:
+            tl[i] = 'N'
+        elif x < 0.02:
+            tl[i] = tl[i].lower()
+    if tl and rng.random() < 0.3:
+        tl[rng.randrange(len(tl))] = rng.choice('RYKM-*xz@+!')
+    if tl and rng.random() < 0.2:
+        tl[rng.randrange(len(tl))] = '\n'
+    return ''.join(tl)
+
+
+def long_cases(ref, rng):
+    """Patterns of 63 .. 512 positions (every length of LONG_M, every distance of LONG_TAU below the length, every text length
+    per pattern length in turn): the reference's hits under every FUZZ_OPTIONS."""
+    cases = []
+    for m in LONG_M:
+        taus = sorted(set(min(t, m - 1) for t in LONG_TAU))
+        for k, tau in enumerate(taus):
+            pat = pattern_of_length(rng, m)
+            L = (0, m - 1, m, m + 5, 600, 1500)[(k + m) % 6]
+            text = long_text(rng, pat, tau, L)
+            hits = [[list(h) for h in ref.string_match(pat, tau, text, opt)] for opt in FUZZ_OPTIONS]
+            cases.append(dict(pattern=pat, tau=tau, text=text, options=list(FUZZ_OPTIONS), hits=hits))
+    return cases
+
+
 def cli(args, path):
     return subprocess.run([REF_BIN] + args + [path], capture_output=True, text=True).stdout
 
@@ -192,5 +239,12 @@ def fuzz_main():
     print("fuzz cases:", len(cases))
 
 
+def long_main():
+    cases = long_cases(Reference(), random.Random(512))
+    with open(os.path.join(HERE, "ref_long_cases.json"), "w") as f:
+        json.dump(cases, f, separators=(",", ":"))
+    print("long cases:", len(cases))
+
+
 if __name__ == "__main__":
-    fuzz_main() if sys.argv[1:] == ["fuzz"] else main()
+    {("fuzz",): fuzz_main, ("long",): long_main}.get(tuple(sys.argv[1:]), main)()

@@ -189,15 +189,17 @@ def test_packed_two_segments_equal_the_ascii_scan(gpu, capi):
 
 
 def test_packed_patterns_the_walk_does_not_serve(gpu, capi, oracle):
-    """No refusal (the reference takes any pattern, libseeq.c:43-138): a 70-position pattern (beyond the two-word column) and patterns
-    without a pair automaton are served by unpacking the batch on the device and scanning that text -- same records as the oracle's."""
+    """No refusal (the reference takes any pattern, libseeq.c:43-138): patterns of 70, 66, 129 and 300 positions (beyond the two-word column:
+    k_forward<4 / 8 / 16> over the unpacked text) and patterns without a pair automaton are served by unpacking the batch on the device and scanning that text -- same records as the oracle's."""
     import torch
     from seeq_amd import device as dev
     sys.path.insert(0, GOLDEN)
     from make_golden import mutate
     rng = random.Random(77)
     long_pat = "".join(rng.choice("ACGT") for _ in range(70))
-    for pattern, tau, L in ((long_pat, 6, 150), ("ACG", 2, 40), ("ACGTA", 4, 33), (long_pat[:64] + "N[AC]", 3, 101)):
+    pat129 = "".join(rng.choice("ACGT") for _ in range(129))           # W = 8
+    pat300 = "".join(rng.choice("ACGT") for _ in range(300))           # W = 16: longer than any read, a read holds a window of it
+    for pattern, tau, L in ((long_pat, 6, 150), ("ACG", 2, 40), ("ACGTA", 4, 33), (long_pat[:64] + "N[AC]", 3, 101), (pat129, 8, 200), (pat300, 60, 256)):
         core = pattern.replace("N", "A").replace("[AC]", "C")
         lines = []
         for i in range(1500):
@@ -206,6 +208,9 @@ def test_packed_patterns_the_walk_does_not_serve(gpu, capi, oracle):
                 cp = mutate(rng, core, rng.randint(0, tau + 2))
                 q = rng.randrange(max(1, L - len(cp) + 1))
                 t = (t[:q] + cp + t[q + len(cp):])[:L]
+            elif i % 3 == 0:
+                q = rng.randrange(len(core) - L + 1)                       # len(core) - L positions are missing: so many edits already
+                t = mutate(rng, core[q:q + L], rng.randint(0, tau + 2 - (len(core) - L)))[:L].ljust(L, "A")
             if i % 9 == 0:
                 q = rng.randrange(L)
                 t = t[:q] + "N" + t[q + 1:]
@@ -216,6 +221,8 @@ def test_packed_patterns_the_walk_does_not_serve(gpu, capi, oracle):
             exp = oracle.buffer_scan(pattern, tau, text, mo)
             got = _packed_scan(dev, torch, pat, text, L, mo, dev.WANT_RECORDS)
             assert got["kernel"] != "k_packed", (pattern, got["kernel"])                 # the fall-back ran
+            if len(core) > 62:
+                assert got["kernel"] == "k_forward" and 0 < exp["nmatchlines"] < 500, (pattern, got["kernel"], exp["nmatchlines"])      # the generic path, hits and near misses
             assert got["nlines"] == exp["nlines"] == len(lines) and got["nmatchlines"] == exp["nmatchlines"], (pattern, tau, L, mo)
             assert np.array_equal(got["records"].astype(np.uint64), exp["records"]), (pattern, tau, L, mo)
         c2 = _packed_scan(dev, torch, pat, text, L, 0, dev.WANT_COUNTMATCH)

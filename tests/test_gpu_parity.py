@@ -1414,9 +1414,10 @@ def test_long_string_match(gpu, capi, oracle):
 def test_string_match_every_size_class(gpu, capi, oracle):
     """seeqStringMatch across the size classes of k_string: read from host memory (<= 4 KiB), staged from device memory,
     positions shared out over the workgroup (<= 32 KiB, more than 64 KiB of LDS beyond 16 KiB), the batched scan beyond
-    -- dense and sparse hits, terminators and N inside, a skipped byte (one-lane scan), one- and two-word patterns."""
+    -- dense and sparse hits, terminators and N inside, a skipped byte (one-lane scan), one-, two- and four-word patterns (the last one
+    stays with k_string at every size; tests/test_gpu_long_patterns.py has W = 8 and 16)."""
     rng = random.Random(2718)
-    for pat, tau in ((PAT20, 3), ("GATGAAGCACGATTAGCCTGAAAATGAGAG", 5), ("ACGT", 1)):
+    for pat, tau in ((PAT20, 3), ("GATGAAGCACGATTAGCCTGAAAATGAGAG", 5), ("ACGT", 1), ("".join(random.Random(70).choice("ACGT") for _ in range(70)), 6)):
         core = pat
         s = SQ(capi, pat, tau)
         for n in (1, 19, 255, 256, 257, 4096, 4097, 8192, 8193, 16000, 20000, 32767, 32768, 32769, 40000):

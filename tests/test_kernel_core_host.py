@@ -116,6 +116,78 @@ def test_string_positions_in_blocks_vs_oracle(harness, oracle, string_cases):
     assert npar > 3000
 
 
+def _long_cases(oracle, nfresh, seed):
+    """(pattern, tau, text, options, hits or None): the reference's long-pattern fixture (tests/golden/ref_long_cases.json), then fresh
+    cases of its generator with distances up to m - 1, the three non-DNA modes and SQ_STREAM (hits None: ask the oracle)."""
+    import json
+    import os
+    sys.path.insert(0, GOLDEN)
+    from make_golden import LONG_M, long_text, pattern_of_length
+    with open(os.path.join(GOLDEN, "ref_long_cases.json")) as f:
+        for c in json.load(f):
+            for opt, hits in zip(c["options"], c["hits"]):
+                yield c["pattern"], c["tau"], c["text"], opt, [tuple(h) for h in hits]
+    rng = random.Random(seed)
+    for i in range(nfresh):
+        m = LONG_M[i % len(LONG_M)]
+        pat = pattern_of_length(rng, m)
+        tau = rng.choice([rng.randint(0, 8), rng.randint(0, m - 1), m - 1, rng.choice([31, 32, 33, 63, 64, 65])])
+        tau = min(tau, m - 1)
+        text = long_text(rng, pat, tau, rng.choice([0, m - 1, m, m + 5, 600, 1500]))
+        for mo in (SQ_FIRST, SQ_BEST, SQ_ALL):
+            yield pat, tau, text, mo | rng.choice([SQ_FAIL, SQ_CONVERT, SQ_IGNORE]) | rng.choice([0, 0, SQ_STREAM]), None
+
+
+def _one_size_up(m):
+    """The next word count the kernels are instantiated for above the pattern's own (0: it has the largest)."""
+    own = next(w for w in (1, 2, 4, 8, 16) if 32 * w >= m)
+    return 2 * own if own < 16 else 0
+
+
+def test_long_patterns_scan_vs_oracle(harness, oracle):
+    """sq_scan_line<W> at real multi-word lengths (63 .. 512 positions: W = 2, 4, 8, 16 with a full last word, one bit in a new word,
+    padded words), distances up to m - 1: records, the any-hit verdict and the count, at the pattern's own word count and one size up."""
+    n = nhits = 0
+    for pat, tau, text, opt, hits in _long_cases(oracle, 360, 6300):
+        exp = (hits if hits is not None else oracle.string_match(pat, tau, text, opt))[::-1]
+        m = len(oracle.parse(pat)[0])
+        for wf in (0, _one_size_up(m)):
+            assert run(harness, oracle, pat, tau, text, opt, EMIT, wf) == exp, (pat, tau, text, opt, wf)
+        allh = oracle.string_match(pat, tau, text, (opt & ~3) | SQ_ALL)
+        assert run(harness, oracle, pat, tau, text, opt, ANY) == (1 if allh else 0), (pat, tau, text, opt)
+        assert run(harness, oracle, pat, tau, text, opt, COUNT, _one_size_up(m) if n % 3 == 0 else 0) == len(allh), (pat, tau, text, opt)
+        n += 1
+        nhits += len(exp)
+    assert n >= 2000 and nhits >= 2000, (n, nhits)
+
+
+def test_long_patterns_string_positions_in_blocks_vs_oracle(harness, oracle):
+    """Host side of k_string<4 / 8 / 16>: a string's positions shared out in blocks of 1, 7, 64 and the whole string, every block from
+    a fresh column (sq_emit_window), at 63 .. 512 positions and distances up to m - 1."""
+    import ctypes as C
+    H = harness
+    H.harness_string_par.restype = C.c_long
+    H.harness_string_par.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_size_t]
+    npar = nhits = 0
+    for i, (pat, tau, text, opt, hits) in enumerate(_long_cases(oracle, 240, 6301)):
+        if len(text) > 700 and i % 4:
+            continue                                       # (block size 1 is O(n x (m + tau)) column steps: a quarter of the long texts)
+        keys, _ = oracle.parse(pat)
+        tb = text.encode("latin-1")
+        exp = (hits if hits is not None else oracle.string_match(pat, tau, text, opt))[::-1]
+        for block in (1, 7, 64, 1 << 20):
+            out = np.zeros(3 * 4096, dtype=np.uint32)
+            wf = _one_size_up(len(keys)) if block == 7 else 0
+            n = H.harness_string_par(tb, len(tb), bytes(keys), len(keys), tau, opt, block, wf, out.ctypes.data, 4096)
+            if n < 0:
+                break                                      # a skipped byte in front of the terminator: the kernel's one-lane scan
+            npar += 1
+            nhits += n
+            assert [tuple(int(x) for x in out[3 * k:3 * k + 3]) for k in range(n)] == exp, (pat, tau, text, opt, block, wf)
+    assert npar >= 2000 and nhits >= 1500, (npar, nhits)
+
+
 def test_stream_automaton_vs_oracle(harness, oracle):
     """Host side of k_stream: the complete Levenshtein automaton (seeq_dfa.h) walked chunk by chunk with a warm-up,
     exactly as the kernel decomposes the text, reports a first-hit event in a line iff the oracle finds a hit in it
@@ -710,6 +782,11 @@ def test_scan_plans_of_the_baseline_configurations(harness):
     assert (p["path"], p["use_myers"], p["fw"], p["stream_ll"], p["filter"]) == (7, 1, 2, 1, 0), p
     # patterns beyond the two-word column, SQ_STREAM input: the generic path; a multi-pattern scan that is not k_pair's: a scan per pattern
     assert plan("ACGT" * 20, 4, 0, COUNTLINES, 151.0)["path"] == 1
+    for m in (63, 512):                                                # the first length beyond the two-word column and the longest there is
+        long_pat = ("GATGTAGCGCGATTAGCCTGAAAATGCGAGTACGGCGCGAAT" * 13)[:m]
+        for opt, want, avg in ((SQ_CONVERT, RECORDS, 151.0), (SQ_IGNORE | SQ_BEST, RECORDS, 151.0), (FASTA | SQ_ALL, RECORDS, 151.0),
+                               (SQ_ALL, RECORDS, 1.3e8), (0, COUNTMATCH, 1.3e8), (SQ_CONVERT | FASTA, COUNTLINES, 1.3e8)):
+            assert plan(long_pat, 8, opt, want, avg)["path"] == 1, (m, opt, want, avg)
     assert plan(head, 3, 0x10, COUNTLINES, 151.0)["path"] in (1, 3)
     assert plan(head, 3, SQ_IGNORE, COUNTLINES, 151.0, flags=32)["rc"] == -2
     # a context that has met a line of a whole tile (force_ll) goes to the long-line variants: k_pair's own (round 5), k_stream's under SQ_IGNORE

@@ -109,6 +109,31 @@ def test_oracle_vs_reference_fuzz(oracle):
                 assert got == reference.string_match(pat, tau, text, opt), (pat, tau, text, opt)
 
 
+def test_oracle_vs_reference_long_patterns(oracle):
+    """The oracle above 70 positions: patterns of 63 .. 512 positions (every length around the 2-, 4-, 8- and 16-word borders of the
+    device's column), distances up to 100, the reference's hits stored in tests/golden/ref_long_cases.json (make_golden.py long);
+    where oracle/_ref is built, against the live reference too."""
+    import sys
+    from oracle.pyoracle import Reference
+    sys.path.insert(0, GOLDEN)
+    from make_golden import LONG_M, plain
+    with open(os.path.join(GOLDEN, "ref_long_cases.json")) as f:
+        cases = json.load(f)
+    reference = Reference() if Reference.available() else None
+    seen, with_hits = set(), 0
+    for c in cases:
+        pat, tau, text = c["pattern"], c["tau"], c["text"]
+        seen.add(len(plain(pat)))
+        with_hits += any(c["hits"])
+        for opt, hits in zip(c["options"], c["hits"]):
+            got = oracle.string_match(pat, tau, text, opt)
+            assert [list(h) for h in got] == hits, (pat, tau, text, opt)
+            if reference is not None:
+                assert got == reference.string_match(pat, tau, text, opt), (pat, tau, text, opt)
+    assert seen == set(LONG_M), sorted(set(LONG_M) ^ seen)
+    assert 2 * with_hits >= len(cases), (with_hits, len(cases))
+
+
 def test_synth_reads_shape(oracle):
     a = oracle.synth_reads(0, 1000, 150, "GATGTAGCGCGATTAGCCTG", 3)
     assert a.size == 1000 * 151 and np.all(a[150::151] == 10)
