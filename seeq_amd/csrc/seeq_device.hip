@@ -807,6 +807,7 @@ static MultiPlan *multi_plan_for(MultiPlan **slot, const seeqdev_pattern_t *cons
 /* Scan context                                                               */
 /* ========================================================================== */
 #include "seeq_plan.h"          /* ScanKnobs, seeq_plan_scan: which kernels serve a scan (pure host code) */
+#include "seeq_workspace.h"     /* Workspace: the owner of a context's buffers -- grouped growth, one free path (pure host code) */
 
 struct OccMemo { const void *fn; size_t lds; int per_cu; };
 
@@ -835,6 +836,7 @@ struct seeqdev_scan {
    bool        last_filter;       /* the last run walked a partition filter automaton */
    bool        last_packed_quad;  /* the last packed run walked the quad table */
    size_t      pk_seg_reads;      /* reads per segment of a packed run */
+   Workspace   ws;                /* owns every device and page-locked buffer below: ws_grow / ws_make bring them into being, ws_free_all ends them */
    /* workspace (device) */
    uint32_t *line_start;  size_t cap_lines;
    uint32_t *tile_cnt;    size_t cap_tiles;
@@ -864,7 +866,7 @@ struct seeqdev_scan {
    Counters *d_cnt;
    Counters *h_cnt;            /* pinned */
    /* seeqdevStringMatch: one string per call in ONE launch (pinned, device-visible) */
-   uint8_t *h_str; size_t cap_str;            /* the string (strings below STRING_ZC_MAX are read by the kernel over the link) */
+   uint8_t *h_str;                            /* the string (strings below STRING_ZC_MAX are read by the kernel over the link) */
    uint32_t *h_strout; size_t cap_strout;     /* {nhits, ticket, pad[2]} + records; fine-grained (coherent) page-locked memory */
    uint32_t  str_seq;                         /* ticket of the last k_string launch */
    /* staging for seeqdevScanHost */
@@ -919,16 +921,23 @@ struct seeqdev_scan {
    unsigned sample_age;        /* runs since the line-length sample was taken (a reused buffer may hold other text by now) */
 };
 
-/* A workspace array of a new size: the new block first, then the old one goes -- a refused allocation (ENOMEM) leaves the array, and with it the
-   capacity its group was sized for, as it was: the context stays usable (tests/test_gpu_parity.py::test_a_refused_reserve_leaves_the_context_usable). */
-static int ws_alloc(void **p, size_t bytes)
+/* The workspace's hooks (seeq_workspace.h).  A refused allocation (ENOMEM) leaves the array, and with it the capacity its group was sized
+   for, as it was: the context stays usable (tests/test_gpu_parity.py::test_a_refused_reserve_leaves_the_context_usable). */
+static void *ws_hip_alloc(void *, int kind, size_t bytes)
 {
    void *g = NULL;
-   hipError_t e = hipMalloc(&g, bytes ? bytes : 16);
-   if (e != hipSuccess) { (void)hipGetLastError(); return hip_fail(e, "hipMalloc(workspace)", ENOMEM); }
-   if (*p) (void)hipFree(*p);
-   *p = g;
-   return 0;
+   const hipError_t e = kind == WS_DEVICE ? hipMalloc(&g, bytes ? bytes : 16)
+                      : hipHostMalloc(&g, bytes ? bytes : 16, kind == WS_COHERENT ? hipHostMallocCoherent : hipHostMallocDefault);
+   if (e == hipSuccess) return g;
+   (void)hipGetLastError();
+   hip_fail(e, kind == WS_DEVICE ? "hipMalloc(workspace)" : "hipHostMalloc(workspace)", ENOMEM);
+   return NULL;
+}
+
+static void ws_hip_release(void *, int kind, void *p)
+{
+   if (kind == WS_DEVICE) (void)hipFree(p);
+   else (void)hipHostFree(p);
 }
 
 extern "C" seeqdev_scan_t *seeqdevScanNew(void *hip_stream)
@@ -942,6 +951,9 @@ extern "C" seeqdev_scan_t *seeqdevScanNew(void *hip_stream)
    seeqdev_scan *s = (seeqdev_scan *)calloc(1, sizeof *s);
    if (!s) return NULL;
    if (hipGetDevice(&s->device) != hipSuccess) s->device = 0;
+   s->ws.hooks = {ws_hip_alloc, ws_hip_release, NULL};
+   /* (these three carry their contents over when they grow -- demux_ws_out, multi_grow_host, seeqdevStringMatch --: grown there, freed with the rest) */
+   ws_adopt(&s->ws, s->dm_out, WS_DEVICE); ws_adopt(&s->ws, s->multi_rec, WS_PINNED); ws_adopt(&s->ws, s->h_strout, WS_COHERENT);
    s->seg_bytes = (size_t)0xF0000000u;      /* 3.75 GiB segments: u32 offsets with room for k_stream's bias; multiple of every tile size */
    const char *env = getenv("SEEQ_SEGMENT_BYTES");
    if (env && atoll(env) >= 65536) s->seg_bytes = ((size_t)atoll(env) + 15) & ~(size_t)15;
@@ -954,11 +966,9 @@ extern "C" seeqdev_scan_t *seeqdevScanNew(void *hip_stream)
       e = hipStreamCreateWithFlags(&s->stream, hipStreamDefault);
       s->own_stream = true;
    }
-   if (e == hipSuccess) e = hipMalloc((void **)&s->d_cnt, sizeof(Counters));
-   if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_cnt, sizeof(Counters), hipHostMallocDefault);
-   if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_eqtab, 2048 * sizeof(uint32_t), hipHostMallocDefault);
-   if (e == hipSuccess) e = hipMalloc((void **)&s->d_eqtab, 2048 * sizeof(uint32_t));
-   if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_sample, SAMPLE_BYTES, hipHostMallocDefault);
+   if (e == hipSuccess && ws_make(&s->ws, {{s->d_cnt, sizeof(Counters)}, {s->h_cnt, sizeof(Counters), WS_PINNED}, {s->h_eqtab, 2048 * sizeof(uint32_t), WS_PINNED},
+                                           {s->d_eqtab, 2048 * sizeof(uint32_t)}, {s->h_sample, SAMPLE_BYTES, WS_PINNED}}))
+      e = hipErrorOutOfMemory;
    {
       const char *pe = getenv("SEEQ_PATH");
       s->force_path = pe ? (!strcmp(pe, "generic") ? 1 : !strcmp(pe, "fused") ? 2 : 0) : 0;
@@ -998,89 +1008,51 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
    (void)use_device(s->device);
    if (s->have_h2d_ev) { (void)hipEventDestroy(s->ev_h2d[0]); (void)hipEventDestroy(s->ev_h2d[1]); }
    (void)hipStreamSynchronize(s->stream);
-   {
-      void *ob[] = {s->ow.tile_cl, s->ow.tile_hits, s->ow.tile_dirty, s->ow.tile_dmask, s->ow.tmp, s->ow.wg_hits, s->ow.wg_part, s->ow.wg_lastnl};
-      for (void *b : ob) if (b) (void)hipFree(b);
-   }
-   { void *pk[] = {s->pk_cand, s->pk_slot, s->pk_coff, s->pk_bmask, s->pk_stage, s->pk_last, s->d_unpack}; for (void *b : pk) if (b) (void)hipFree(b); }
-   { void *mw[] = {s->ml_mask, s->ml_first, s->ml_last, s->mp_idx, s->mp_nh, s->m_bsum, s->d_mcnt, s->d_mx, s->m_scan_ws}; for (void *b : mw) if (b) (void)hipFree(b); }
-   { void *dm[] = {s->dm_key, s->dm_aux, s->dm_out, s->d_dmcnt}; for (void *b : dm) if (b) (void)hipFree(b); }
-   if (s->h_dmcnt) (void)hipHostFree(s->h_dmcnt);
-   if (s->h_mcnt) (void)hipHostFree(s->h_mcnt);
-   if (s->h_mx) (void)hipHostFree(s->h_mx);
+   ws_free_all(&s->ws);
    multi_plan_free(s->mplan);
-   void *bufs[] = {s->rec_off, s->line_start, s->tile_cnt, s->hitmask, s->hdrmask, s->wave_off, s->hdr_off, s->hit_start,
-                   s->hit_line, s->d_eqtab,
-                   s->nh, s->hit_col, s->nh_sum, s->ent, s->records, s->scan_ws, s->lead_fidx, s->lead_flag, s->lead_wend, s->lead_key, s->d_cnt, s->d_text};
-   for (void *b : bufs) if (b) (void)hipFree(b);
-   if (s->h_cnt) (void)hipHostFree(s->h_cnt);
-   if (s->h_eqtab) (void)hipHostFree(s->h_eqtab);
-   if (s->h_sample) (void)hipHostFree(s->h_sample);
-   if (s->h_str) (void)hipHostFree(s->h_str);
-   if (s->h_strout) (void)hipHostFree(s->h_strout);
    for (size_t i = 0; i < 4 * s->nev_seg; i++) (void)hipEventDestroy(s->ev[i]);
    free(s->ev);
    free(s->launch_ms);
-   if (s->clk_probe) (void)hipHostFree(s->clk_probe);
    free(s->multi_cnt); free(s->multi_first);
-   if (s->multi_rec) (void)hipHostFree(s->multi_rec);
    if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
    free(s);
+}
+
+/* block sums of the two-level scans (launch_scan, launch_scanset, the packed and demux rank scans): room for nblocks of them */
+static int ensure_scan_ws(seeqdev_scan *s, size_t nblocks)
+{
+   return ws_grow(&s->ws, &s->cap_scan_ws, nblocks, {{s->scan_ws, nblocks * sizeof(uint32_t)}});
 }
 
 static int reserve_impl(seeqdev_scan *s, size_t max_bytes, size_t max_lines, size_t max_hitlines, size_t max_records)
 {
    seeqerr = 0;
    if (!s) { errno = EINVAL; return -1; }
+   Workspace *w = &s->ws;
    /* Everything per-line is per SEGMENT; only records span the whole buffer. */
    if (max_bytes) {
       const size_t seg = max_bytes < s->seg_bytes ? max_bytes : s->seg_bytes;
       const size_t tiles = (seg + TILE - 1) / TILE + 1;
-      if (tiles > s->cap_tiles) {
-         if (ws_alloc((void **)&s->tile_cnt, tiles * sizeof(uint32_t))) return -1;
-         s->cap_tiles = tiles;
-      }
+      if (ws_grow(w, &s->cap_tiles, tiles, {{s->tile_cnt, tiles * sizeof(uint32_t)}})) return -1;
       const size_t ftiles = seg / FUSED_MIN_TILE + 2;
       const size_t slices = MAX_FUSED_GRID;               /* hit slices: one per wave of a persistent grid */
-      if (ftiles > s->cap_ftiles) {
-         if (ws_alloc((void **)&s->ow.tile_cl, ftiles * sizeof(uint32_t))) return -1;
-         if (ws_alloc((void **)&s->ow.tile_dirty, ftiles * sizeof(uint32_t))) return -1;
-         if (ws_alloc((void **)&s->ow.tile_dmask, ftiles * sizeof(uint64_t))) return -1;
-         if (ws_alloc((void **)&s->ow.tile_hits, ftiles * sizeof(uint32_t))) return -1;
-         s->cap_ftiles = ftiles;
-      }
-      if (slices > s->cap_slices) {
-         if (ws_alloc((void **)&s->ow.wg_hits, slices * sizeof(uint32_t))) return -1;
-         if (ws_alloc((void **)&s->ow.wg_part, 4 * slices * sizeof(uint32_t))) return -1;
-         if (ws_alloc((void **)&s->ow.wg_lastnl, slices * sizeof(uint32_t))) return -1;
-         s->cap_slices = slices;
-      }
+      if (ws_grow(w, &s->cap_ftiles, ftiles, {{s->ow.tile_cl, ftiles * sizeof(uint32_t)}, {s->ow.tile_dirty, ftiles * sizeof(uint32_t)},
+                                              {s->ow.tile_dmask, ftiles * sizeof(uint64_t)}, {s->ow.tile_hits, ftiles * sizeof(uint32_t)}})) return -1;
+      if (ws_grow(w, &s->cap_slices, slices, {{s->ow.wg_hits, slices * sizeof(uint32_t)}, {s->ow.wg_part, 4 * slices * sizeof(uint32_t)},
+                                              {s->ow.wg_lastnl, slices * sizeof(uint32_t)}})) return -1;
    }
    if (max_lines > s->cap_lines) {
       const size_t chunks = (max_lines + 63) / 64 + 1;
-      if (ws_alloc((void **)&s->line_start, (max_lines + 1) * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->hitmask, chunks * sizeof(uint64_t))) return -1;
-      if (ws_alloc((void **)&s->hdrmask, chunks * sizeof(uint64_t))) return -1;
-      if (ws_alloc((void **)&s->wave_off, chunks * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->hdr_off, chunks * sizeof(uint32_t))) return -1;
-      s->cap_lines = max_lines;
+      if (ws_grow(w, &s->cap_lines, max_lines, {{s->line_start, (max_lines + 1) * sizeof(uint32_t)}, {s->hitmask, chunks * sizeof(uint64_t)},
+                                                {s->hdrmask, chunks * sizeof(uint64_t)}, {s->wave_off, chunks * sizeof(uint32_t)},
+                                                {s->hdr_off, chunks * sizeof(uint32_t)}})) return -1;
       s->cap_chunks = chunks;
    }
-   if (max_hitlines > s->cap_hitlines) {
-      if (ws_alloc((void **)&s->hit_start, max_hitlines * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->hit_line, max_hitlines * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->ow.tmp, max_hitlines * sizeof(uint4))) return -1;
-      if (ws_alloc((void **)&s->nh, max_hitlines * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->hit_col, max_hitlines * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->ent, max_hitlines * sizeof(uint4))) return -1;
-      if (ws_alloc((void **)&s->nh_sum, 2 * (max_hitlines / 256 + 2) * sizeof(uint32_t))) return -1;      /* + the chunks' entries with a hit */
-      s->cap_hitlines = max_hitlines;
-   }
-   if (max_records > s->cap_records) {
-      if (ws_alloc((void **)&s->records, max_records * sizeof(seeqdev_hit_t))) return -1;
-      if (ws_alloc((void **)&s->rec_off, max_records * sizeof(uint64_t))) return -1;
-      s->cap_records = max_records;
-   }
+   if (ws_grow(w, &s->cap_hitlines, max_hitlines, {{s->hit_start, max_hitlines * sizeof(uint32_t)}, {s->hit_line, max_hitlines * sizeof(uint32_t)},
+                                                   {s->ow.tmp, max_hitlines * sizeof(uint4)}, {s->nh, max_hitlines * sizeof(uint32_t)},
+                                                   {s->hit_col, max_hitlines * sizeof(uint32_t)}, {s->ent, max_hitlines * sizeof(uint4)},
+                                                   {s->nh_sum, 2 * (max_hitlines / 256 + 2) * sizeof(uint32_t)}})) return -1;      /* (nh_sum: + the chunks' entries with a hit) */
+   if (ws_grow(w, &s->cap_records, max_records, {{s->records, max_records * sizeof(seeqdev_hit_t)}, {s->rec_off, max_records * sizeof(uint64_t)}})) return -1;
    /* block sums for the two-level scans: the largest scanned array */
    size_t largest = s->cap_tiles;
    if (s->cap_chunks > largest) largest = s->cap_chunks;
@@ -1088,11 +1060,7 @@ static int reserve_impl(seeqdev_scan *s, size_t max_bytes, size_t max_lines, siz
    if (s->cap_ftiles > largest) largest = s->cap_ftiles;
    size_t nb = largest / SCAN_BLOCK + 2;
    if (3 * (s->cap_ftiles / SCAN_BLOCK + 2) > nb) nb = 3 * (s->cap_ftiles / SCAN_BLOCK + 2);   /* launch_scanset: three tile arrays at once */
-   if (nb > s->cap_scan_ws) {
-      if (ws_alloc((void **)&s->scan_ws, nb * sizeof(uint32_t))) return -1;
-      s->cap_scan_ws = nb;
-   }
-   return 0;
+   return ensure_scan_ws(s, nb);
 }
 
 extern "C" int seeqdevScanReserve(seeqdev_scan_t *s, size_t max_bytes, size_t max_lines, size_t max_hitlines,
@@ -1304,8 +1272,14 @@ static int prof_events(seeqdev_scan *s, size_t nseg)
       hipEvent_t *g = (hipEvent_t *)realloc(s->ev, 4 * nseg * sizeof(hipEvent_t));
       if (!g) { seeqerr = 0; errno = ENOMEM; return -1; }
       s->ev = g;
-      for (size_t i = 4 * s->nev_seg; i < 4 * nseg; i++) HIP_TRY(hipEventCreate(&s->ev[i]), EIO);
-      s->nev_seg = nseg;
+      while (s->nev_seg < nseg) {                          /* a segment counts once its four events exist: seeqdevScanFree destroys those and no others */
+         hipEvent_t *e4 = s->ev + 4 * s->nev_seg;
+         for (int i = 0; i < 4; i++) {
+            const hipError_t e = hipEventCreate(&e4[i]);
+            if (e != hipSuccess) { while (i--) (void)hipEventDestroy(e4[i]); return hip_fail(e, "hipEventCreate", EIO); }
+         }
+         s->nev_seg++;
+      }
    }
    s->prof_segs = nseg;
    return 0;
@@ -1435,9 +1409,9 @@ static int run_setup(seeqdev_scan *s, SegRun &r)
    r.nseg = nbytes ? (nbytes + r.seg_bytes - 1) / r.seg_bytes : 0;
    if (prof_events(s, r.nseg)) return -1;
    if (s->prof && r.nseg > s->cap_clk_probe) {
-      if (s->clk_probe) (void)hipHostFree(s->clk_probe);
-      s->clk_probe = nullptr; s->cap_clk_probe = 0;
-      if (hipHostMalloc((void **)&s->clk_probe, r.nseg * 4 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess) s->cap_clk_probe = r.nseg;
+      ws_release(&s->ws, s->clk_probe);                    /* (nothing to carry over: the old block goes first; a refusal leaves profiling without the clock) */
+      s->cap_clk_probe = 0;
+      if (ws_make(&s->ws, {{s->clk_probe, r.nseg * 4 * sizeof(unsigned long long), WS_PINNED}}) == 0) s->cap_clk_probe = r.nseg;
    }
    if (s->prof && s->clk_probe) memset(s->clk_probe, 0, r.nseg * 4 * sizeof(unsigned long long));
    s->clk_valid = s->prof && s->clk_probe && plan.use_pair && plan.use_fused;
@@ -1587,13 +1561,9 @@ static int seg_post(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipEvent_t *e
    /* long lines, every hit counted: candidates far behind the one before them get a lane of their own (seeq_stream.h, leaders) */
    const uint32_t lead_wback = a.skip_back > 32u ? a.skip_back : 32u;
    if (plan.leaders) {
-      if (s->cap_hitlines > s->cap_lead) {
-         if (ws_alloc((void **)&s->lead_fidx, s->cap_hitlines * sizeof(uint32_t))) return -1;
-         if (ws_alloc((void **)&s->lead_flag, s->cap_hitlines * sizeof(uint32_t))) return -1;
-         if (ws_alloc((void **)&s->lead_wend, s->cap_hitlines * sizeof(uint32_t))) return -1;
-         if (ws_alloc((void **)&s->lead_key, s->cap_hitlines * sizeof(unsigned long long))) return -1;
-         s->cap_lead = s->cap_hitlines;
-      }
+      if (ws_grow(&s->ws, &s->cap_lead, s->cap_hitlines, {{s->lead_fidx, s->cap_hitlines * sizeof(uint32_t)}, {s->lead_flag, s->cap_hitlines * sizeof(uint32_t)},
+                                                          {s->lead_wend, s->cap_hitlines * sizeof(uint32_t)},
+                                                          {s->lead_key, s->cap_hitlines * sizeof(unsigned long long)}})) return -1;
       const unsigned nbl = (unsigned)(s->cap_hitlines / LEAD_BLOCK + 1);
       hipLaunchKernelGGL(k_lead_reduce, dim3(nbl), dim3(256), 0, st, a, s->scan_ws);
       hipLaunchKernelGGL(k_lead_top, dim3(1), dim3(256), 0, st, a, s->scan_ws);
@@ -1753,25 +1723,12 @@ static int run_packed(seeqdev_scan *s)
       PACKED_SEG_READS = (stage_lines_max - 64u * MAX_FUSED_GRID) & ~(size_t)63;
    const size_t seg_reads = b.nreads < PACKED_SEG_READS ? (size_t)b.nreads : PACKED_SEG_READS;
    const size_t cap_use = (!direct && s->cap_hitlines > stage_lines_max) ? stage_lines_max : s->cap_hitlines;      /* hit-list entries a segment may make */
-   if (seg_reads > s->cap_pk_reads) {
-      if (ws_alloc((void **)&s->pk_cand, seg_reads * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->pk_slot, seg_reads * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->pk_coff, (seg_reads / 64 + 1) * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->pk_bmask, (seg_reads / 64 + 1) * sizeof(uint64_t))) return -1;
-      s->cap_pk_reads = seg_reads;
-   }
-   if (!direct && cap_use * (size_t)pitch > s->cap_pk_stage) {
-      if (ws_alloc((void **)&s->pk_stage, cap_use * (size_t)pitch + 64)) return -1;
-      s->cap_pk_stage = cap_use * (size_t)pitch;
-   }
-   if (s->cap_hitlines > s->cap_pk_last) {
-      if (ws_alloc((void **)&s->pk_last, s->cap_hitlines * sizeof(uint32_t))) return -1;
-      s->cap_pk_last = s->cap_hitlines;
-   }
-   {  /* block sums of the scans over per-read arrays */
-      const size_t nb = seg_reads / SCAN_BLOCK + 2;
-      if (nb > s->cap_scan_ws) { if (ws_alloc((void **)&s->scan_ws, nb * sizeof(uint32_t))) return -1; s->cap_scan_ws = nb; }
-   }
+   if (ws_grow(&s->ws, &s->cap_pk_reads, seg_reads, {{s->pk_cand, seg_reads * sizeof(uint32_t)}, {s->pk_slot, seg_reads * sizeof(uint32_t)},
+                                                     {s->pk_coff, (seg_reads / 64 + 1) * sizeof(uint32_t)},
+                                                     {s->pk_bmask, (seg_reads / 64 + 1) * sizeof(uint64_t)}})) return -1;
+   if (!direct && ws_grow(&s->ws, &s->cap_pk_stage, cap_use * (size_t)pitch, {{s->pk_stage, cap_use * (size_t)pitch + 64}})) return -1;
+   if (ws_grow(&s->ws, &s->cap_pk_last, s->cap_hitlines, {{s->pk_last, s->cap_hitlines * sizeof(uint32_t)}})) return -1;
+   if (ensure_scan_ws(s, seg_reads / SCAN_BLOCK + 2)) return -1;      /* block sums of the scans over per-read arrays */
    /* EQ tables of the exact pass (as run_segments makes them) */
    if (eq_tables_upload(s, pat, options, fw)) return -1;
    HIP_TRY(hipMemsetAsync(c, 0, sizeof(Counters), st), EIO);
@@ -1868,40 +1825,20 @@ static int run_packed(seeqdev_scan *s)
 /* ========================================================================== */
 static int multi_ws_ensure(seeqdev_scan *s, int npat)
 {
-   if (!s->d_mcnt) {
-      HIP_TRY(hipMalloc((void **)&s->d_mcnt, SEEQ_MULTI_MAX * sizeof(Counters)), ENOMEM);
-      HIP_TRY(hipHostMalloc((void **)&s->h_mcnt, SEEQ_MULTI_MAX * sizeof(Counters), hipHostMallocDefault), ENOMEM);
-   }
-   if (s->cap_hitlines > s->cap_ml) {
-      if (ws_alloc((void **)&s->ml_mask, s->cap_hitlines * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->ml_first, s->cap_hitlines * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->ml_last, s->cap_hitlines * sizeof(uint32_t))) return -1;
-      s->cap_ml = s->cap_hitlines;
-   }
-   if (s->cap_hitlines > s->cap_mp) {
-      if (ws_alloc((void **)&s->mp_idx, s->cap_hitlines * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->mp_nh, s->cap_hitlines * sizeof(uint32_t))) return -1;
-      s->cap_mp = s->cap_hitlines;
-   }
+   Workspace *w = &s->ws;
+   const size_t hl = s->cap_hitlines;
+   if (ws_make(w, {{s->d_mcnt, SEEQ_MULTI_MAX * sizeof(Counters)}, {s->h_mcnt, SEEQ_MULTI_MAX * sizeof(Counters), WS_PINNED}})) return -1;
+   if (ws_grow(w, &s->cap_ml, hl, {{s->ml_mask, hl * sizeof(uint32_t)}, {s->ml_first, hl * sizeof(uint32_t)}, {s->ml_last, hl * sizeof(uint32_t)}})) return -1;
+   if (ws_grow(w, &s->cap_mp, hl, {{s->mp_idx, hl * sizeof(uint32_t)}, {s->mp_nh, hl * sizeof(uint32_t)}})) return -1;
    if (!s->d_mx) {
-      s->mx_slots = 64;                                    /* segments whose argument arrays may be in flight (a run of more segments waits for the stream in between) */
-      HIP_TRY(hipMalloc((void **)&s->d_mx, s->mx_slots * SEEQ_MULTI_MAX * sizeof(MultiExact)), ENOMEM);
-      HIP_TRY(hipHostMalloc((void **)&s->h_mx, s->mx_slots * SEEQ_MULTI_MAX * sizeof(MultiExact), hipHostMallocDefault), ENOMEM);
+      const size_t slots = 64;                             /* segments whose argument arrays may be in flight (a run of more segments waits for the stream in between) */
+      if (ws_make(w, {{s->d_mx, slots * SEEQ_MULTI_MAX * sizeof(MultiExact)}, {s->h_mx, slots * SEEQ_MULTI_MAX * sizeof(MultiExact), WS_PINNED}})) return -1;
+      s->mx_slots = slots;
       s->mx_next = 0;
    }
-   {
-      const size_t nbp = (s->cap_hitlines / (size_t)npat) / SCAN_BLOCK + 2;
-      if ((size_t)npat * nbp > s->cap_m_scan_ws) {
-         if (ws_alloc((void **)&s->m_scan_ws, (size_t)npat * nbp * sizeof(uint32_t))) return -1;
-         s->cap_m_scan_ws = (size_t)npat * nbp;
-      }
-   }
-   const size_t nb = s->cap_hitlines / MULTI_BLOCK + 2;
-   if ((size_t)npat * nb > s->cap_m_bsum) {
-      if (ws_alloc((void **)&s->m_bsum, (size_t)npat * nb * sizeof(uint32_t))) return -1;
-      s->cap_m_bsum = (size_t)npat * nb;
-   }
-   return 0;
+   const size_t nbp = (hl / (size_t)npat) / SCAN_BLOCK + 2, nb = hl / MULTI_BLOCK + 2;
+   if (ws_grow(w, &s->cap_m_scan_ws, (size_t)npat * nbp, {{s->m_scan_ws, (size_t)npat * nbp * sizeof(uint32_t)}})) return -1;
+   return ws_grow(w, &s->cap_m_bsum, (size_t)npat * nb, {{s->m_bsum, (size_t)npat * nb * sizeof(uint32_t)}});
 }
 
 /* The part of a segment behind the union walk: `ua` = the union scan's arguments (hit list made, bounds done). */
@@ -2191,10 +2128,7 @@ extern "C" int seeqdevScanPacked(seeqdev_scan_t *s, const seeqdev_pattern_t *pat
       /* not the packed walk's pattern (more than 62 positions, or no pair automaton): the batch is unpacked on the device and the
          ASCII scan runs over it -- the reference takes any pattern (libseeq.c:43-138), so does this entry */
       const size_t tbytes = (size_t)batch->nreads * (batch->read_len + 1u);
-      if (tbytes > s->cap_unpack) {
-         if (ws_alloc((void **)&s->d_unpack, tbytes + 64)) return -1;
-         s->cap_unpack = tbytes;
-      }
+      if (ws_grow(&s->ws, &s->cap_unpack, tbytes, {{s->d_unpack, tbytes + 64}})) return -1;
       if (batch->nreads) {
          const uint64_t threads = batch->nreads * (uint64_t)(batch->read_len / 16u + 1u), blocks = (threads + 255) / 256;
          if (blocks > 0x7FFFFFFFull) { errno = E2BIG; return -1; }
@@ -2399,15 +2333,19 @@ extern "C" int seeqdevScanCopyOffsets(seeqdev_scan_t *s, uint64_t *host_out, siz
    return 0;
 }
 
+/* The context's staging buffer holds nbytes (grown with a quarter to spare) */
+static int text_ensure(seeqdev_scan *s, size_t nbytes)
+{
+   if (nbytes <= s->cap_text) return 0;
+   const size_t cap = nbytes + (nbytes >> 2) + 4096;
+   return ws_grow(&s->ws, &s->cap_text, cap, {{s->d_text, cap}});
+}
+
 /* Host text into the context's staging buffer, on its stream (timed: between the H2D events).  New contents behind the same pointer:
    the line length is sampled again */
 static int text_upload(seeqdev_scan *s, const char *host_text, size_t nbytes, bool timed)
 {
-   if (nbytes > s->cap_text) {
-      const size_t cap = nbytes + (nbytes >> 2) + 4096;
-      if (ws_alloc((void **)&s->d_text, cap)) return -1;
-      s->cap_text = cap;
-   }
+   if (text_ensure(s, nbytes)) return -1;
    if (timed) HIP_TRY(hipEventRecord(s->ev_h2d[0], s->stream), EIO);
    if (nbytes) HIP_TRY(hipMemcpyAsync(s->d_text, host_text, nbytes, hipMemcpyHostToDevice, s->stream), EIO);
    if (timed) HIP_TRY(hipEventRecord(s->ev_h2d[1], s->stream), EIO);
@@ -2630,18 +2568,9 @@ extern "C" int seeqdevScanMultiRecords(const seeqdev_scan_t *s, int k, const see
 /* Per-line workspace for nkeys lines (8 bytes per line; allocated by the first demux of a context), keys cleared. */
 static int demux_ws_lines(seeqdev_scan *s, size_t nkeys)
 {
-   if (!s->d_dmcnt && ws_alloc((void **)&s->d_dmcnt, sizeof(DemuxCnt))) return -1;
-   if (!s->h_dmcnt) HIP_TRY(hipHostMalloc((void **)&s->h_dmcnt, sizeof(DemuxCnt), hipHostMallocDefault), ENOMEM);
-   if (nkeys > s->cap_dm_lines) {
-      if (ws_alloc((void **)&s->dm_key, nkeys * sizeof(uint32_t))) return -1;
-      if (ws_alloc((void **)&s->dm_aux, nkeys * sizeof(uint32_t))) return -1;
-      s->cap_dm_lines = nkeys;
-   }
-   const size_t nb = nkeys / SCAN_BLOCK + 2;               /* block sums of the rank scan: the context's scan workspace */
-   if (nb > s->cap_scan_ws) {
-      if (ws_alloc((void **)&s->scan_ws, nb * sizeof(uint32_t))) return -1;
-      s->cap_scan_ws = nb;
-   }
+   if (ws_make(&s->ws, {{s->d_dmcnt, sizeof(DemuxCnt)}, {s->h_dmcnt, sizeof(DemuxCnt), WS_PINNED}})) return -1;
+   if (ws_grow(&s->ws, &s->cap_dm_lines, nkeys, {{s->dm_key, nkeys * sizeof(uint32_t)}, {s->dm_aux, nkeys * sizeof(uint32_t)}})) return -1;
+   if (ensure_scan_ws(s, nkeys / SCAN_BLOCK + 2)) return -1;      /* block sums of the rank scan: the context's scan workspace */
    if (nkeys) HIP_TRY(hipMemsetAsync(s->dm_key, 0, nkeys * sizeof(uint32_t), s->stream), EIO);
    HIP_TRY(hipMemsetAsync(s->d_dmcnt, 0, sizeof(DemuxCnt), s->stream), EIO);
    return 0;
@@ -2992,24 +2921,18 @@ extern "C" int seeqdevStringMatch(seeqdev_scan_t *s, const seeqdev_pattern_t *pa
    if (!s || !pat || (!data && n) || !rec || !nrec) { errno = EINVAL; return -1; }
    if (n > 0xFFFF0000ull) { errno = E2BIG; return -1; }
    if (use_device(s->device)) return -1;
-   if (!s->h_strout) {
-      s->cap_strout = 256;                                  /* records */
-      HIP_TRY(hipHostMalloc((void **)&s->h_strout, 16 + s->cap_strout * sizeof(seeqdev_hit_t), hipHostMallocCoherent), ENOMEM);
-   }
-   if (!s->h_str) {
-      s->cap_str = STRING_ZC_MAX + 16;
-      HIP_TRY(hipHostMalloc((void **)&s->h_str, s->cap_str, hipHostMallocDefault), ENOMEM);
+   if (!s->h_strout || !s->h_str) {
+      const size_t nrec0 = 256;                             /* records */
+      const bool first_out = !s->h_strout;
+      if (ws_make(&s->ws, {{s->h_strout, 16 + nrec0 * sizeof(seeqdev_hit_t), WS_COHERENT}, {s->h_str, STRING_ZC_MAX + 16, WS_PINNED}})) return -1;
+      if (first_out) s->cap_strout = nrec0;
    }
    const uint8_t *dtext;
    if (n <= STRING_ZC_MAX) {
       memcpy(s->h_str, data, n);
       dtext = s->h_str;                                     /* page-locked host memory is device-visible at the same address */
    } else {
-      if (n > s->cap_text) {
-         const size_t cap = n + (n >> 2) + 4096;
-         if (ws_alloc((void **)&s->d_text, cap)) return -1;
-         s->cap_text = cap;
-      }
+      if (text_ensure(s, n)) return -1;
       HIP_TRY(hipMemcpyAsync(s->d_text, data, n, hipMemcpyHostToDevice, s->stream), EIO);
       s->avg_text = NULL;
       dtext = s->d_text;

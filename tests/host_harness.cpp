@@ -433,3 +433,120 @@ extern "C" int harness_plan(const char *keys, int m, int tau, int options, int w
    for (int i = 0; i < 16; i++) out[i] = v[i];
    return 0;
 }
+
+// ---- the owner of a scan context's buffers (seeq_amd/csrc/seeq_workspace.h): the same code seeqdev_scan embeds, over FAKE hooks --
+//      malloc-backed, every live block kept in a table (a release of a block that is not live, or of the wrong kind, is counted), the
+//      N-th request refused on demand.  harness_ws_script runs the call pattern of a context: first growths of five capacity groups
+//      (1 to 7 members), two fixed-size sets, a second and larger growth of every group, everything once more (what a caller does
+//      after ENOMEM: it asks again), then free-all.  One row of 14 numbers per step:
+//        0 step kind (0 grow, 1 make, 2 free-all)   1 group / set   2 rc   3 capacity before   4 after   5 wanted
+//        6 requests so far   7 live blocks   8 registered slots that hold a pointer (free-all: member pointers of the context that do)
+//        9 bad releases so far   10 members of the group / set that hold a pointer   11 its members
+//        12 slots that were on a live block before the step and are not now
+//        13 members whose block is smaller than the last completed growth of their group asked for
+//      Returns the number of steps.
+#include "../seeq_amd/csrc/seeq_workspace.h"
+
+namespace {
+struct FakeMem {
+   struct { void *p; size_t bytes; int kind; } live[128];
+   int  nlive;
+   long requests, refuse_at, bad;
+   long size_of(const void *p) const { for (int i = 0; i < nlive; i++) if (live[i].p == p) return (long)live[i].bytes; return -1; }
+};
+void *fake_alloc(void *ctx, int kind, size_t bytes)
+{
+   FakeMem *f = (FakeMem *)ctx;
+   if (++f->requests == f->refuse_at || f->nlive == 128) return NULL;
+   void *p = malloc(bytes ? bytes : 16);
+   if (!p) return NULL;
+   f->live[f->nlive].p = p; f->live[f->nlive].bytes = bytes; f->live[f->nlive].kind = kind;
+   f->nlive++;
+   return p;
+}
+void fake_release(void *ctx, int kind, void *p)
+{
+   FakeMem *f = (FakeMem *)ctx;
+   for (int i = 0; i < f->nlive; i++)
+      if (f->live[i].p == p && f->live[i].kind == kind) { free(p); f->live[i] = f->live[--f->nlive]; return; }
+   f->bad++;                                               // never handed out, handed back already, or of another kind
+}
+
+// a stand-in for seeqdev_scan: member pointers of several types, capacities beside them
+struct FakeCtx {
+   Workspace ws;
+   uint32_t *tile_cl, *tile_dirty, *tile_hits; uint64_t *tile_dmask; size_t cap_ftiles;
+   uint32_t *line_start, *wave_off, *hdr_off; uint64_t *hitmask, *hdrmask; size_t cap_lines;
+   uint32_t *hit_start, *hit_line, *nh, *hit_col, *nh_sum; uint64_t *tmp, *ent; size_t cap_hitlines;
+   uint32_t *wg_hits, *wg_part, *wg_lastnl; size_t cap_slices;
+   uint32_t *scan_ws; size_t cap_scan_ws;
+   uint64_t *d_cnt, *h_cnt;
+   uint8_t *h_str; uint32_t *h_strout;
+   size_t need[WS_MAX_SLOTS];                               // per registry entry: the bytes its group's last completed growth asked for
+};
+
+// one call (cap: ws_grow to n; NULL: ws_make) and what it left behind -> columns 2-4, 10, 11, 13 of the row
+void ws_call(FakeCtx &c, const FakeMem &f, size_t *cap, size_t n, std::initializer_list<WsMember> ms, long long *r)
+{
+   const size_t cap0 = cap ? *cap : 0;
+   const int rc = cap ? ws_grow(&c.ws, cap, n, ms) : ws_make(&c.ws, ms);
+   int held = 0, small = 0;
+   for (const WsMember &m : ms) {
+      const int k = ws_adopt(&c.ws, m.slot, m.kind);
+      if (rc == 0 && (!cap || n > cap0)) c.need[k] = m.bytes;
+      if (*m.slot) held++;
+      if (*m.slot ? f.size_of(*m.slot) < (long)c.need[k] : c.need[k] != 0) small++;
+   }
+   r[2] = rc; r[3] = (long long)cap0; r[4] = cap ? (long long)*cap : 0; r[10] = held; r[11] = (long long)ms.size(); r[13] = small;
+}
+
+void ws_step(FakeCtx &c, const FakeMem &f, int kind, int g, size_t n, long long *r)
+{
+   if (kind == 0 && g == 0) ws_call(c, f, &c.cap_ftiles, n, {{c.tile_cl, n * 4}, {c.tile_dirty, n * 4}, {c.tile_dmask, n * 8}, {c.tile_hits, n * 4}}, r);
+   else if (kind == 0 && g == 1) ws_call(c, f, &c.cap_lines, n, {{c.line_start, (n + 1) * 4}, {c.hitmask, n * 8}, {c.hdrmask, n * 8}, {c.wave_off, n * 4}, {c.hdr_off, n * 4}}, r);
+   else if (kind == 0 && g == 2) ws_call(c, f, &c.cap_hitlines, n, {{c.hit_start, n * 4}, {c.hit_line, n * 4}, {c.tmp, n * 16}, {c.nh, n * 4}, {c.hit_col, n * 4}, {c.ent, n * 16},
+                                                                   {c.nh_sum, 2 * (n / 256 + 2) * 4}}, r);
+   else if (kind == 0 && g == 3) ws_call(c, f, &c.cap_slices, n, {{c.wg_hits, n * 4}, {c.wg_part, 4 * n * 4}, {c.wg_lastnl, n * 4}}, r);
+   else if (kind == 0) ws_call(c, f, &c.cap_scan_ws, n, {{c.scan_ws, n * 4}}, r);
+   else if (g == 0) ws_call(c, f, NULL, 0, {{c.d_cnt, 64}, {c.h_cnt, 64, WS_PINNED}}, r);
+   else ws_call(c, f, NULL, 0, {{c.h_strout, 16 + 256 * 16, WS_COHERENT}, {c.h_str, 4096 + 16, WS_PINNED}}, r);
+}
+}  // namespace
+
+extern "C" int harness_ws_members(void) { return 4 + 5 + 7 + 3 + 1 + 2 + 2; }
+
+extern "C" int harness_ws_script(long refuse_at, long long *rows, int max_rows)
+{
+   static const struct { int kind, g; size_t n; } steps[] = {
+      {0, 0, 300}, {0, 3, 1024}, {0, 1, 5000}, {0, 2, 700}, {1, 0, 0}, {0, 4, 40}, {1, 0, 0}, {1, 1, 0},      // a reserve, the first scans
+      {0, 1, 90000}, {0, 2, 12000}, {0, 0, 301}, {0, 3, 2048}, {0, 4, 4000},                                 // the re-run on overflow: everything larger
+      {0, 1, 90000}, {0, 2, 12000}, {0, 0, 301}, {0, 3, 2048}, {0, 4, 4000}, {1, 0, 0}, {1, 1, 0},           // the caller asks again
+      {2, 0, 0}};
+   FakeMem f;
+   FakeCtx c;
+   std::memset(&f, 0, sizeof f);
+   std::memset(&c, 0, sizeof c);
+   f.refuse_at = refuse_at;
+   c.ws.hooks = {fake_alloc, fake_release, &f};
+   int ns = 0;
+   for (const auto &st : steps) {
+      if (ns == max_rows) break;
+      long long *r = rows + (size_t)14 * ns++;
+      std::memset(r, 0, 14 * sizeof *r);
+      void **was_live[WS_MAX_SLOTS];                        // the registered slots that are on a live block before the step
+      int nwas = 0, lost = 0, held = 0;
+      for (int i = 0; i < c.ws.nreg; i++) if (f.size_of(*c.ws.reg[i].slot) >= 0) was_live[nwas++] = c.ws.reg[i].slot;
+      if (st.kind == 2) {
+         ws_free_all(&c.ws);
+         void *const all[] = {c.tile_cl, c.tile_dirty, c.tile_hits, c.tile_dmask, c.line_start, c.wave_off, c.hdr_off, c.hitmask, c.hdrmask, c.hit_start, c.hit_line,
+                              c.nh, c.hit_col, c.nh_sum, c.tmp, c.ent, c.wg_hits, c.wg_part, c.wg_lastnl, c.scan_ws, c.d_cnt, c.h_cnt, c.h_str, c.h_strout};
+         for (void *p : all) if (p) held++;
+      } else {
+         ws_step(c, f, st.kind, st.g, st.n, r);
+         for (int i = 0; i < nwas; i++) if (f.size_of(*was_live[i]) < 0) lost++;
+         for (int i = 0; i < c.ws.nreg; i++) if (*c.ws.reg[i].slot) held++;
+      }
+      r[0] = st.kind; r[1] = st.g; r[5] = (long long)st.n; r[6] = f.requests; r[7] = f.nlive; r[8] = held; r[9] = f.bad; r[12] = lost;
+   }
+   return ns;
+}

@@ -794,3 +794,62 @@ def test_scan_plans_of_the_baseline_configurations(harness):
     assert (p["path"], p["use_pair"], p["stream_ll"], p["window_ok"], p["order2"]) == (6, 1, 1, 0, 0), p
     p = plan(head, 3, SQ_BEST | SQ_IGNORE, RECORDS, 151.0, flags=1)
     assert (p["use_pair"], p["stream_ll"]) == (0, 1) or p["path"] in (1, 3), p
+
+
+def test_workspace_growth_is_grouped_and_every_refusal_leaves_it_whole(harness):
+    """The owner of a scan context's buffers (seeq_workspace.h) over fake hooks (host_harness.cpp: harness_ws_script): the call pattern of a
+    context -- first growths of five capacity groups, two fixed-size sets, a larger growth of every group, every call once more, free-all --
+    run clean, then once for EVERY request of the clean run with that request refused.  After every step the live blocks are the pointers the
+    registered slots hold, nothing is released twice or unasked, no slot has lost its block or sits on one smaller than its group's capacity
+    says; the refused call returns -1 with its capacity untouched (a fixed-size set: with none of its slots set) and the same call made again
+    succeeds."""
+    import ctypes as C
+    H = harness
+    H.harness_ws_script.restype = C.c_int
+    H.harness_ws_script.argtypes = [C.c_long, C.c_void_p, C.c_int]
+    GROW, MAKE, FREE = 0, 1, 2
+    cols = ("kind", "g", "rc", "cap0", "cap", "want", "requests", "live", "held", "bad", "set_held", "members", "lost", "small")
+
+    def script(refuse_at):
+        rows = np.zeros((64, len(cols)), dtype=np.int64)
+        n = H.harness_ws_script(refuse_at, rows.ctypes.data, 64)
+        assert 0 < n < 64
+        return [dict(zip(cols, (int(v) for v in row))) for row in rows[:n]]
+
+    def check_invariants(rows, tag):
+        for i, r in enumerate(rows):
+            assert r["live"] == r["held"], (tag, i, r)             # a block that exists is registered, a registered pointer is a live block
+            assert r["bad"] == 0 and r["lost"] == 0 and r["small"] == 0, (tag, i, r)
+            if r["kind"] == GROW and r["rc"] == 0:
+                assert r["cap"] == max(r["cap0"], r["want"]) and r["set_held"] == r["members"], (tag, i, r)
+            if r["kind"] == MAKE and r["rc"] == 0:
+                assert r["set_held"] == r["members"], (tag, i, r)
+        assert rows[-1]["kind"] == FREE and rows[-1]["live"] == 0 and rows[-1]["held"] == 0, (tag, rows[-1])
+
+    clean = script(0)
+    check_invariants(clean, "clean")
+    assert all(r["rc"] == 0 for r in clean)
+    total = clean[-1]["requests"]
+    assert total >= H.harness_ws_members() >= 24                   # every member of every group and set was requested at least once
+    assert max(r["live"] for r in clean) == H.harness_ws_members()
+    final_cap = {r["g"]: r["cap"] for r in clean if r["kind"] == GROW}
+    for n in range(1, total + 1):
+        rows = script(n)
+        check_invariants(rows, n)
+        failed = [i for i, r in enumerate(rows) if r["rc"] != 0]
+        assert len(failed) == 1, (n, failed)                       # the N-th request exists in every run: exactly one call meets the refusal
+        i = failed[0]
+        r = rows[i]
+        assert r["rc"] == -1 and r["kind"] in (GROW, MAKE) and r["requests"] >= n > (rows[i - 1]["requests"] if i else 0), (n, r)
+        if r["kind"] == GROW:
+            assert r["cap"] == r["cap0"] < r["want"], (n, r)
+        else:
+            assert r["set_held"] == 0, (n, r)                      # all or nothing
+        # the script goes on: the same group grows later, the same set is made later
+        later = [q for q in rows[i + 1:] if (q["kind"], q["g"]) == (r["kind"], r["g"])]
+        assert later and all(q["rc"] == 0 for q in later), (n, r)
+        if r["kind"] == GROW:
+            assert later[0]["cap"] == later[0]["want"] > r["cap0"], (n, later[0])
+        else:
+            assert later[0]["set_held"] == later[0]["members"], (n, later[0])
+        assert {q["g"]: q["cap"] for q in rows if q["kind"] == GROW} == final_cap, n
