@@ -44,6 +44,28 @@ extern "C" {
 #define SEEQDEV_FASTA       0x100   /* lines starting with '>' are headers: skipped, not counted (seeq.c:367-374) */
 #define SEEQDEV_SINGLELINE  0x200   /* the buffer is ONE string (seeqStringMatch semantics, libseeq.c:171): no
                                        newline index; with SQ_STREAM newlines are skipped (libseeq.c:265)  */
+#define SEEQDEV_FASTQ       0x400   /* the buffer is four-line FASTQ records: only the sequence lines count (below)   */
+
+/* SEEQDEV_FASTQ.  The buffer is a sequence of four-line FASTQ records, taken purely BY POSITION: raw line 4r + 2 (1-based) is the
+ * sequence line of record r + 1; nothing looks for '@' or '+', and a trailing partial record counts when its sequence line is
+ * there.  (Without the flag a FASTQ buffer is scanned as plain lines: headers, '+' lines and quality strings -- Phred+33 holds
+ * A, C and G -- give records of their own, numbered by raw line.)  Every observable result is that of the same call, with the
+ * same `options` and `want`, over a buffer that holds the sequence lines alone -- seeqdev_hit_t.line / seeqdev_demux_t.line is the
+ * 1-based RECORD number, nlines = (raw lines + 2) / 4, nmatchlines / nhits / nrecords / nassigned / nambiguous / per_pattern count
+ * sequence lines only, seeqdevScanRecordsDevice / CopyRecords / CopyOffsets / DemuxDevice / CopyDemux see the filtered, still
+ * ordered arrays -- with two exceptions: seeqdevScanCopyOffsets reports each record's sequence-line offset in the ORIGINAL
+ * buffer, and nheaders is 0.
+ * Accepted by seeqdevScanRun, seeqdevScanHostBegin, seeqdevScanHost (seeqdevScanFetch completes it) and seeqdevScanRunDemux /
+ * seeqdevScanHostDemux.  EINVAL: together with SEEQDEV_FASTA, SEEQDEV_SINGLELINE or SQ_STREAM; given to seeqdevScanPacked,
+ * seeqdevScanRunMulti / seeqdevScanHostMulti or seeqdevStringMatch.
+ * How, and what it costs: the scan kernels run unchanged over all four lines, and seeqdevScanFetch (the demultiplexer: its last
+ * step) runs one ordered compaction of the records on the device (seeq_fastq.h: three launches, at most 24 bytes read and
+ * written per record).  A context that has been given the flag keeps a second record array and a second offset array
+ * (16 + 8 bytes per record of workspace capacity, sized by seeqdevScanReserve's max_records like the first; allocated by the
+ * context's first flagged call, so a seeqdevScanReserve AFTER that call is the one after which Run and Fetch do not allocate).
+ * The workspace must hold the records of all four lines.  SEEQDEV_WANT_COUNTLINES / COUNTMATCH have no records to filter: under the
+ * flag the scan runs for records (SQ_FIRST / SQ_ALL) and the counts come from the filter -- nrecords is 0 and
+ * seeqdevScanCopyRecords refuses as ever, but the count modes need record workspace for EVERY hit of the buffer. */
 
 /* One hit.  `line` is the 1-based index among counted lines of the scanned
  * buffer (reference seeq.c:377); `end` is exclusive (libseeq.h:62-66).

@@ -21,7 +21,7 @@ SQ_LINES, SQ_STREAM = 0x00, 0x10
 SQ_ANY, SQ_MATCH, SQ_NOMATCH, SQ_COUNTLINES, SQ_COUNTMATCH = 0, 1, 2, 3, 4
 # seeq_amd.h
 WANT_COUNTLINES, WANT_COUNTMATCH, WANT_RECORDS = 0, 1, 2
-SEEQDEV_FASTA, SEEQDEV_SINGLELINE = 0x100, 0x200
+SEEQDEV_FASTA, SEEQDEV_SINGLELINE, SEEQDEV_FASTQ = 0x100, 0x200, 0x400
 
 
 class match_t(C.Structure):

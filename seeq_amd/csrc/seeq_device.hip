@@ -448,6 +448,7 @@ __global__ void k_single_line(ScanArgs a)
 #include "seeq_packed.h"
 #include "seeq_multi.h"
 #include "seeq_demux.h"
+#include "seeq_fastq.h"
 static_assert(sizeof(seeqdev_demux_t) == 16 && sizeof(seeqdev_hit_t) == sizeof(uint4), "demux records are written as uint4");
 #include "seeq_post.h"
 static_assert(STREAM_NW == STREAM_NW_HOST, "waves per k_stream workgroup");
@@ -861,6 +862,14 @@ struct seeqdev_scan {
    int force_path;                /* 0 auto, 1 generic, 2 fused (SEEQ_PATH env / tests) */
    int last_path;                 /* 1 generic, 2 fused: what the last run used */
    seeqdev_hit_t *records; uint64_t *rec_off; size_t cap_records;
+   /* SEEQDEV_FASTQ (seeq_fastq.h): the filter's output arrays -- swapped with records / rec_off after a filter, so both pairs hold cap_records
+      entries -- and its per-tile sums; only on contexts that were given the flag (fq_ws), grown with the record arrays */
+   seeqdev_hit_t *fq_rec; uint64_t *fq_off; uint32_t *fq_bsum; size_t cap_fq;
+   FastqCnt *d_fqcnt, *h_fqcnt;   /* h_ pinned */
+   bool fq_ws;                    /* the context has been given SEEQDEV_FASTQ: the scratch above follows cap_records from now on */
+   bool fastq;                    /* the last run was given the flag (options / want below are those of the internal, unflagged scan) */
+   bool fq_done;                  /* ... and seeqdevScanFetch has filtered its records */
+   int  fq_want;                  /* ... and this is the `want` its caller passed */
    uint32_t *scan_ws;           size_t cap_scan_ws;
    uint32_t *lead_fidx, *lead_flag, *lead_wend; unsigned long long *lead_key; size_t cap_lead;      /* long lines, leaders (seeq_stream.h): per hit-list entry */
    Counters *d_cnt;
@@ -1024,6 +1033,9 @@ static int ensure_scan_ws(seeqdev_scan *s, size_t nblocks)
    return ws_grow(&s->ws, &s->cap_scan_ws, nblocks, {{s->scan_ws, nblocks * sizeof(uint32_t)}});
 }
 
+/* the filter's per-tile sums for n records (seeq_fastq.h: kept and opened per tile) */
+static size_t fastq_bsum_words(size_t n) { return 2 * (n / SEEQ_FASTQ_TILE + 2); }
+
 static int reserve_impl(seeqdev_scan *s, size_t max_bytes, size_t max_lines, size_t max_hitlines, size_t max_records)
 {
    seeqerr = 0;
@@ -1052,7 +1064,19 @@ static int reserve_impl(seeqdev_scan *s, size_t max_bytes, size_t max_lines, siz
                                                    {s->ow.tmp, max_hitlines * sizeof(uint4)}, {s->nh, max_hitlines * sizeof(uint32_t)},
                                                    {s->hit_col, max_hitlines * sizeof(uint32_t)}, {s->ent, max_hitlines * sizeof(uint4)},
                                                    {s->nh_sum, 2 * (max_hitlines / 256 + 2) * sizeof(uint32_t)}})) return -1;      /* (nh_sum: + the chunks' entries with a hit) */
-   if (ws_grow(w, &s->cap_records, max_records, {{s->records, max_records * sizeof(seeqdev_hit_t)}, {s->rec_off, max_records * sizeof(uint64_t)}})) return -1;
+   if (s->fq_ws && max_records > s->cap_records) {
+      /* the filter's scratch grows with the record arrays, as one group */
+      if (ws_grow(w, &s->cap_records, max_records, {{s->records, max_records * sizeof(seeqdev_hit_t)}, {s->rec_off, max_records * sizeof(uint64_t)},
+                                                    {s->fq_rec, max_records * sizeof(seeqdev_hit_t)}, {s->fq_off, max_records * sizeof(uint64_t)},
+                                                    {s->fq_bsum, fastq_bsum_words(max_records) * sizeof(uint32_t)}})) return -1;
+      s->cap_fq = s->cap_records;
+   } else if (ws_grow(w, &s->cap_records, max_records, {{s->records, max_records * sizeof(seeqdev_hit_t)}, {s->rec_off, max_records * sizeof(uint64_t)}})) return -1;
+   if (s->fq_ws) {
+      /* (record arrays from before the context's first flagged scan: the scratch catches up) */
+      const size_t n = s->cap_records;
+      if (ws_grow(w, &s->cap_fq, n, {{s->fq_rec, n * sizeof(seeqdev_hit_t)}, {s->fq_off, n * sizeof(uint64_t)}, {s->fq_bsum, fastq_bsum_words(n) * sizeof(uint32_t)}})) return -1;
+      if (ws_make(w, {{s->d_fqcnt, sizeof(FastqCnt)}, {s->h_fqcnt, sizeof(FastqCnt), WS_PINNED}})) return -1;
+   }
    /* block sums for the two-level scans: the largest scanned array */
    size_t largest = s->cap_tiles;
    if (s->cap_chunks > largest) largest = s->cap_chunks;
@@ -1978,7 +2002,20 @@ static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const voi
       errno = EINVAL;
       return -1;
    }
+   const bool fastq = (options & SEEQDEV_FASTQ) != 0;
+   if (fastq && (options & (SEEQDEV_FASTA | SEEQDEV_SINGLELINE | MASK_INPUT))) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
+   s->fastq = fastq; s->fq_done = false; s->fq_want = want;
+   if (fastq) {
+      /* the scan itself runs unflagged (a re-run in seeqdevScanFetch too: it reads s->options / s->want); the count wants have
+         no records to filter, so under the flag they are scanned for records: one per matching line, or every hit */
+      s->fq_ws = true;
+      options &= ~SEEQDEV_FASTQ;
+      if (want != SEEQDEV_WANT_RECORDS) {
+         options = (options & ~MASK_MATCH) | (want == SEEQDEV_WANT_COUNTLINES ? SQ_FIRST : SQ_ALL);
+         want = SEEQDEV_WANT_RECORDS;
+      }
+   }
    s->pat = pat; s->text = d_text; s->nbytes = nbytes; s->options = options; s->want = want;
    s->ran = false;
    s->is_packed = false;
@@ -2025,6 +2062,71 @@ static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const voi
 /* The capacity a re-run asks for where a workspace overflowed: what the device reported it needs, plus an eighth */
 static size_t grown(uint64_t need) { return (size_t)need + (size_t)(need >> 3) + 64; }
 
+/* SEEQDEV_FASTQ: the filter of seeq_fastq.h over the first n records of `in` (with their line offsets, or NULL) into the context's
+   scratch arrays, on its stream; the filter's counters follow to h_fqcnt.  Asynchronous; n > 0. */
+static int fastq_launch(seeqdev_scan *s, const void *in, const uint64_t *off_in, uint32_t n, bool demux)
+{
+   const hipStream_t st = s->stream;
+   FastqArgs a;
+   memset(&a, 0, sizeof a);
+   a.in = (const uint4 *)in; a.off_in = off_in;
+   a.out = (uint4 *)s->fq_rec; a.off_out = s->fq_off;
+   a.n = n; a.cap_out = (uint32_t)(s->cap_fq < 0xFFFFFFFFull ? s->cap_fq : 0xFFFFFFFFull);
+   a.nb = (uint32_t)(((uint64_t)n + SEEQ_FASTQ_TILE - 1) / SEEQ_FASTQ_TILE);
+   a.bsum = s->fq_bsum;
+   a.cnt = s->d_fqcnt;
+   if (!s->fq_rec || !s->d_fqcnt || n > s->cap_fq || fastq_bsum_words(s->cap_fq) < 2 * (size_t)a.nb) {
+      snprintf(g_last_error, sizeof g_last_error, "FASTQ filter: %u records, scratch for %zu", n, s->cap_fq);
+      errno = EIO;
+      return -1;
+   }
+   HIP_TRY(hipMemsetAsync(s->d_fqcnt, 0, sizeof(FastqCnt), st), EIO);
+   if (demux) hipLaunchKernelGGL(k_fastq_reduce<true>, dim3(a.nb), dim3(SEEQ_FASTQ_WG), 0, st, a);
+   else hipLaunchKernelGGL(k_fastq_reduce<false>, dim3(a.nb), dim3(SEEQ_FASTQ_WG), 0, st, a);
+   hipLaunchKernelGGL(k_fastq_top, dim3(1), dim3(SEEQ_FASTQ_WG), 0, st, a);
+   hipLaunchKernelGGL(k_fastq_apply, dim3(a.nb), dim3(SEEQ_FASTQ_WG), 0, st, a);
+   HIP_TRY(hipGetLastError(), EIO);
+   HIP_TRY(hipMemcpyAsync(s->h_fqcnt, s->d_fqcnt, sizeof(FastqCnt), hipMemcpyDeviceToHost, st), EIO);
+   return 0;
+}
+
+/* The flagged scan has converged with the counters h: filter its records, swap the filtered arrays in, fill s->counts. */
+static int fastq_finish(seeqdev_scan *s, const Counters &h)
+{
+   if (h.records > 0xFFFFFFFFull) {
+      snprintf(g_last_error, sizeof g_last_error, "SEEQDEV_FASTQ: more than 2^32 - 1 records to filter");
+      errno = E2BIG;
+      return -1;
+   }
+   const uint32_t n = (uint32_t)h.records;
+   uint32_t kept = 0, opened = 0;
+   if (n) {
+      if (s->cap_fq != s->cap_records) {
+         snprintf(g_last_error, sizeof g_last_error, "FASTQ filter: scratch for %zu records, record workspace for %zu", s->cap_fq, s->cap_records);
+         errno = EIO;
+         return -1;
+      }
+      if (fastq_launch(s, s->records, s->rec_off, n, false)) return -1;
+      HIP_TRY(hipStreamSynchronize(s->stream), EIO);
+      const FastqCnt &f = *s->h_fqcnt;
+      if (f.bad || f.kept > n || f.opened > f.kept) {
+         snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the FASTQ filter (flags %u, %u of %u kept, %u lines)", f.bad, f.kept, n, f.opened);
+         errno = EIO;
+         return -1;
+      }
+      kept = f.kept; opened = f.opened;
+      /* the filtered arrays become the context's records; what was scanned into is the next filter's scratch (no copy back) */
+      seeqdev_hit_t *r = s->records; s->records = s->fq_rec; s->fq_rec = r;
+      uint64_t *o = s->rec_off; s->rec_off = s->fq_off; s->fq_off = o;
+   }
+   s->counts.nlines = fastq_nlines(h.lines);
+   s->counts.nmatchlines = opened;
+   s->counts.nhits = s->fq_want == SEEQDEV_WANT_COUNTLINES ? opened : kept;
+   s->counts.nrecords = s->fq_want == SEEQDEV_WANT_RECORDS ? kept : 0;
+   s->counts.nheaders = 0;
+   return 0;
+}
+
 extern "C" int seeqdevScanFetch(seeqdev_scan_t *s, seeqdev_counts_t *counts)
 {
    seeqerr = 0;
@@ -2036,11 +2138,16 @@ extern "C" int seeqdevScanFetch(seeqdev_scan_t *s, seeqdev_counts_t *counts)
       HIP_TRY(hipStreamSynchronize(s->stream), EIO);
       const Counters h = *s->h_cnt;
       if (!h.overflow) {
-         s->counts.nlines = h.lines;
-         s->counts.nmatchlines = h.matchlines;
-         s->counts.nhits = h.hits;
-         s->counts.nrecords = h.records;
-         s->counts.nheaders = h.headers;
+         if (s->fastq) {
+            if (!s->fq_done && fastq_finish(s, h)) return -1;
+            s->fq_done = true;
+         } else {
+            s->counts.nlines = h.lines;
+            s->counts.nmatchlines = h.matchlines;
+            s->counts.nhits = h.hits;
+            s->counts.nrecords = h.records;
+            s->counts.nheaders = h.headers;
+         }
          if (counts) *counts = s->counts;
          for (int i = 0; i < 4; i++) s->acc_ms[i] = 0.f;
          s->fwd_ms_avg = 0.f;
@@ -2118,9 +2225,10 @@ extern "C" int seeqdevScanPacked(seeqdev_scan_t *s, const seeqdev_pattern_t *pat
    seeqerr = 0;
    if (!s || !pat || !batch || want < 0 || want > 2 || (batch->nreads && !batch->bases)) { errno = EINVAL; return -1; }
    if (batch->read_len < 1 || batch->read_len > 256 || batch->stride < (batch->read_len + 3) / 4 ||
-       (batch->nmask && batch->nstride < (batch->read_len + 7) / 8) || (options & (MASK_INPUT | SEEQDEV_FASTA | SEEQDEV_SINGLELINE))) { errno = EINVAL; return -1; }
+       (batch->nmask && batch->nstride < (batch->read_len + 7) / 8) || (options & (MASK_INPUT | SEEQDEV_FASTA | SEEQDEV_SINGLELINE | SEEQDEV_FASTQ))) { errno = EINVAL; return -1; }
    if (pat->device != s->device) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
+   s->fastq = false;
    seeqdev_pattern *mp = const_cast<seeqdev_pattern *>(pat);
    if (pat->wlen <= FUSED_MAX_WLEN2 && __atomic_load_n(&mp->pair_state, __ATOMIC_ACQUIRE) == 0) pattern_plan_pair(mp);
    if (pat->wlen <= FUSED_MAX_WLEN2 && mp->pair_state == 1 && __atomic_load_n(&mp->quad_state, __ATOMIC_ACQUIRE) == 0) pattern_plan_quad(mp);
@@ -2507,7 +2615,7 @@ extern "C" int seeqdevScanRunMulti(seeqdev_scan_t *s, const seeqdev_pattern_t *c
                                    int options, int want, seeqdev_counts_t *counts)
 {
    seeqerr = 0;
-   if (!s || !pats || npat < 1 || (!d_text && nbytes) || want < 0 || want > 2) { errno = EINVAL; return -1; }
+   if (!s || !pats || npat < 1 || (!d_text && nbytes) || want < 0 || want > 2 || (options & SEEQDEV_FASTQ)) { errno = EINVAL; return -1; }
    if (npat > s->cap_multi_n) {
       seeqdev_counts_t *c = (seeqdev_counts_t *)realloc(s->multi_cnt, (size_t)npat * sizeof *c);
       if (c) s->multi_cnt = c;
@@ -2548,7 +2656,7 @@ extern "C" int seeqdevScanHostMulti(seeqdev_scan_t *s, const seeqdev_pattern_t *
                                     int options, int want, seeqdev_counts_t *counts)
 {
    seeqerr = 0;
-   if (!s || !pats || npat < 1 || (!host_text && nbytes)) { errno = EINVAL; return -1; }
+   if (!s || !pats || npat < 1 || (!host_text && nbytes) || (options & SEEQDEV_FASTQ)) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
    if (text_upload(s, host_text, nbytes, false)) return -1;      /* once, for all patterns */
    return seeqdevScanRunMulti(s, pats, npat, s->d_text, nbytes, options, want, counts);
@@ -2711,10 +2819,47 @@ static int demux_per_pattern(seeqdev_scan_t *s, const seeqdev_pattern_t *const *
    return demux_finish(s, nkeys, npat, nullptr, 0);
 }
 
+/* SEEQDEV_FASTQ: the demultiplexer's records (one per assigned raw line, in line order) reduced to those of the sequence lines and
+   numbered by record -- the filter of seeq_fastq.h in its demux mode, whose tallies replace the counters of demux_finish.  The filter
+   never writes in place: its output comes back from the scratch with one device copy (dm_out has a capacity of its own and carries its
+   contents over when it grows, so it cannot be swapped with the scratch as the record arrays are). */
+static int demux_fastq(seeqdev_scan *s)
+{
+   s->dm_nlines = fastq_nlines(s->dm_nlines);
+   DemuxCnt &h = *s->h_dmcnt;
+   const size_t n = s->dm_nrec;
+   uint32_t kept = 0;
+   memset(h.per_pat, 0, sizeof h.per_pat);
+   h.ambiguous = 0;
+   if (n) {
+      if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
+      if (reserve_impl(s, 0, 0, 0, n)) return -1;
+      if (fastq_launch(s, s->dm_out, nullptr, (uint32_t)n, true)) return -1;
+      HIP_TRY(hipStreamSynchronize(s->stream), EIO);
+      const FastqCnt &f = *s->h_fqcnt;
+      if (f.bad || f.kept > n) {
+         snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the FASTQ filter (flags %u, %u of %zu kept)", f.bad, f.kept, n);
+         errno = EIO;
+         return -1;
+      }
+      kept = f.kept;
+      if (kept) {
+         HIP_TRY(hipMemcpyAsync(s->dm_out, s->fq_rec, (size_t)kept * sizeof(uint4), hipMemcpyDeviceToDevice, s->stream), EIO);
+         HIP_TRY(hipStreamSynchronize(s->stream), EIO);
+      }
+      for (int k = 0; k < 256; k++) h.per_pat[k] = f.per_pat[k];
+      h.ambiguous = f.ambiguous;
+   }
+   h.nassigned = kept;
+   s->dm_nrec = kept;
+   return 0;
+}
+
 static int demux_args_ok(const seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *text, size_t nbytes, int options,
                          const seeqdev_demux_counts_t *sum)
 {
    if (!s || !pats || npat < 1 || npat > SEEQ_DEMUX_MAX || (!text && nbytes) || !sum || (options & MASK_MATCH) >= SQ_ALL) return 0;
+   if ((options & SEEQDEV_FASTQ) && (options & (SEEQDEV_FASTA | SEEQDEV_SINGLELINE | MASK_INPUT))) return 0;
    for (int k = 0; k < npat; k++) if (!pats[k]) return 0;
    return 1;
 }
@@ -2725,7 +2870,9 @@ extern "C" int seeqdevScanRunDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *c
    seeqerr = 0;
    if (!demux_args_ok(s, pats, npat, d_text, nbytes, options, sum)) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
-   const int opts = (options & ~MASK_MATCH) | SQ_BEST;
+   const bool fastq = (options & SEEQDEV_FASTQ) != 0;
+   const int opts = (options & ~(MASK_MATCH | SEEQDEV_FASTQ)) | SQ_BEST;      /* (the set's scans run unflagged: demux_fastq filters their result) */
+   if (fastq) s->fq_ws = true;
    s->dm_nrec = 0;
    s->dm_nlines = 0;
    s->multi_n = 0;                                         /* (no multi results on the host: seeqdevScanMultiRecords refuses) */
@@ -2734,6 +2881,7 @@ extern "C" int seeqdevScanRunDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *c
    int rc = multi_one_pass(s, pats, npat, d_text, nbytes, opts, SEEQDEV_WANT_RECORDS, nullptr, true);
    if (rc == 1) rc = demux_per_pattern(s, pats, npat, d_text, nbytes, opts);
    scan_forget(s);                                         /* (the patterns are the caller's) */
+   if (rc == 0 && fastq) rc = demux_fastq(s);
    if (rc) { s->dm_nrec = 0; return -1; }
    const DemuxCnt &h = *s->h_dmcnt;
    sum->nlines = s->dm_nlines;
@@ -2918,7 +3066,7 @@ extern "C" int seeqdevStringMatch(seeqdev_scan_t *s, const seeqdev_pattern_t *pa
                                   const seeqdev_hit_t **rec, size_t *nrec)
 {
    seeqerr = 0;
-   if (!s || !pat || (!data && n) || !rec || !nrec) { errno = EINVAL; return -1; }
+   if (!s || !pat || (!data && n) || !rec || !nrec || (options & SEEQDEV_FASTQ)) { errno = EINVAL; return -1; }
    if (n > 0xFFFF0000ull) { errno = E2BIG; return -1; }
    if (use_device(s->device)) return -1;
    if (!s->h_strout || !s->h_str) {

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (SQ_ALL, SQ_BEST, SQ_CONVERT, SQ_FAIL, SQ_FIRST, SQ_IGNORE, SEEQDEV_FASTA,  # noqa: F401
+from ._capi import (SQ_ALL, SQ_BEST, SQ_CONVERT, SQ_FAIL, SQ_FIRST, SQ_IGNORE, SEEQDEV_FASTA, SEEQDEV_FASTQ,  # noqa: F401
                     WANT_COUNTLINES, WANT_COUNTMATCH, WANT_RECORDS)
 
 
@@ -191,7 +191,10 @@ class Scanner:
         return [float(ms[i]) for i in range(max(0, min(got, n)))]
 
     def run(self, pattern, d_ptr, nbytes, options=0, want=WANT_COUNTLINES):
-        """Enqueue the scan (asynchronous)."""
+        """Enqueue the scan (asynchronous).  options: libseeq.h bits | SEEQDEV_FASTA | SEEQDEV_FASTQ -- with SEEQDEV_FASTQ the buffer is
+        four-line FASTQ records taken by position, and everything fetch() / records() / record_offsets() report is that of a scan of the
+        sequence lines alone: `line` is the 1-based record number, nlines counts records; record_offsets() are offsets of the
+        sequence lines in THIS buffer (seeq_amd.h)."""
         _check(self._lib.seeqdevScanRun(self._h, pattern.handle, C.c_void_p(d_ptr), nbytes, options, want))
 
     def fetch(self):
@@ -231,7 +234,7 @@ class Scanner:
         _check(self._lib.seeqdevScanPacked(self._h, pattern.handle, C.byref(b), options, want))
 
     def scan_host(self, pattern, data, options=0, want=WANT_COUNTLINES):
-        """data: bytes.  H2D + scan + fetch (+ records when want == WANT_RECORDS)."""
+        """data: bytes.  H2D + scan + fetch (+ records when want == WANT_RECORDS).  options may hold SEEQDEV_FASTQ (see run)."""
         cnt = _capi.seeqdev_counts_t()
         _check(self._lib.seeqdevScanHost(self._h, pattern.handle, data, len(data), options, want, C.byref(cnt)))
         res = dict(nlines=cnt.nlines, nmatchlines=cnt.nmatchlines, nhits=cnt.nhits, nrecords=cnt.nrecords,
@@ -306,7 +309,8 @@ class Scanner:
 
     def demux_host(self, patterns, data, options=0):
         """data: bytes, staged once.  Per line the best pattern of the set, demultiplexed on the device -> dict: nlines, nassigned,
-        nambiguous, assigned (lines won per pattern), records (one per assigned line, in line order; DEMUX_DTYPE)."""
+        nambiguous, assigned (lines won per pattern), records (one per assigned line, in line order; DEMUX_DTYPE).  With SEEQDEV_FASTQ in
+        options only the sequence lines of four-line FASTQ records count: `line` is the record number, nlines counts records."""
         return self._demux(patterns, lambda arr, n, cnt, per: self._lib.seeqdevScanHostDemux(self._h, arr, n, data, len(data), options, cnt, per), True)
 
     def demux_tensor(self, patterns, t, options=0, copy=True):
