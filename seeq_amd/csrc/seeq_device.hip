@@ -809,6 +809,7 @@ static MultiPlan *multi_plan_for(MultiPlan **slot, const seeqdev_pattern_t *cons
 /* ========================================================================== */
 #include "seeq_plan.h"          /* ScanKnobs, seeq_plan_scan: which kernels serve a scan (pure host code) */
 #include "seeq_workspace.h"     /* Workspace: the owner of a context's buffers -- grouped growth, one free path (pure host code) */
+#include "seeq_rerun.h"         /* the first reservation, what follows a run that came back void, the fall-back flags (pure host code) */
 
 struct OccMemo { const void *fn; size_t lds; int per_cu; };
 
@@ -919,13 +920,7 @@ struct seeqdev_scan {
    float fwd_ms_avg;           /* mean k_forward launch duration of the last run */
    size_t seg_bytes;           /* segment size */
    bool user_reserved;         /* caller sized the per-line workspace: trust it */
-   bool no_stream;             /* k_stream met a line it cannot address (starts > 1 GiB before its segment): use the per-line kernels */
-   bool force_ll;              /* a read-length looking buffer had hits inside very long lines: use k_stream's long-line variant */
-   bool no_stream_nd;          /* SQ_CONVERT / SQ_IGNORE: the text has non-DNA bytes, k_stream (exact for clean text only) is off */
-   bool no_leaders;            /* long lines with many hits: a leader's fresh start lay inside the walk before it -- every line stays with one lane */
-   bool no_window;             /* k_pair's candidates: a line had candidates on both sides of a segment seam -- whole lines are scanned */
-   int  fallback_ttl;          /* scans left before the fall-back flags above are dropped and the fast path is tried again (one text with a
-                                  long line or foreign bytes must not slow a long-lived context down for good) */
+   RerunFallback fallback;     /* what earlier runs reported of the text: kernels the planner stays off for the next scans (seeq_rerun.h) */
    bool sample_dirty;          /* the sampled prefix holds more than one byte outside the alphabet per 4 KB: FASTA input stays off k_pair */
    unsigned sample_age;        /* runs since the line-length sample was taken (a reused buffer may hold other text by now) */
 };
@@ -1371,8 +1366,9 @@ static int run_setup(seeqdev_scan *s, SegRun &r)
    memset(&pin, 0, sizeof pin);
    pin.wlen = pat->wlen; pin.tau = pat->tau; pin.options = s->options; pin.want = s->want;
    pin.avg_line = s->avg_line; pin.line_hint = s->line_hint; pin.force_path = s->force_path;
-   pin.no_stream = s->no_stream; pin.force_ll = s->force_ll; pin.no_stream_nd = s->no_stream_nd; pin.no_window = s->no_window;
-   pin.no_leaders = s->no_leaders; pin.sample_dirty = s->sample_dirty; pin.multi_active = s->multi_active;
+   const RerunFallback &fb = s->fallback;
+   pin.no_stream = fb.no_stream(); pin.force_ll = fb.force_ll(); pin.no_stream_nd = fb.no_stream_nd(); pin.no_window = fb.no_window();
+   pin.no_leaders = fb.no_leaders(); pin.sample_dirty = s->sample_dirty; pin.multi_active = s->multi_active;
    pin.seg_bytes = s->seg_bytes; pin.kn = &s->knobs;
    PlanAutomata au;
    pattern_automata(pat, &au);
@@ -1985,7 +1981,7 @@ static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const voi
 extern "C" int seeqdevScanRun(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const void *d_text, size_t nbytes,
                               int options, int want)
 {
-   if (scan_setup(s, pat, d_text, nbytes, options, want, 8)) return -1;
+   if (scan_setup(s, pat, d_text, nbytes, options, want, SEEQ_HL_DIV)) return -1;
    if (dispatch_run(s)) return -1;
    s->ran = true;
    return 0;
@@ -2007,7 +2003,7 @@ static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const voi
    if (use_device(s->device)) return -1;
    s->fastq = fastq; s->fq_done = false; s->fq_want = want;
    if (fastq) {
-      /* the scan itself runs unflagged (a re-run in seeqdevScanFetch too: it reads s->options / s->want); the count wants have
+      /* the scan itself runs unflagged (a re-run of seeqdevScanFetch too: it reads s->options / s->want); the count wants have
          no records to filter, so under the flag they are scanned for records: one per matching line, or every hit */
       s->fq_ws = true;
       options &= ~SEEQDEV_FASTQ;
@@ -2019,21 +2015,11 @@ static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const voi
    s->pat = pat; s->text = d_text; s->nbytes = nbytes; s->options = options; s->want = want;
    s->ran = false;
    s->is_packed = false;
-   if ((s->no_stream || s->no_stream_nd || s->force_ll || s->no_window || s->no_leaders) && --s->fallback_ttl <= 0) s->no_stream = s->no_stream_nd = s->force_ll = s->no_window = s->no_leaders = false;
-   /* Optimistic default workspace: lines average >= 32 bytes, one line in 8 hits, 1 record per hit line.
-      A too-small workspace is detected on the device and fixed by one re-run in seeqdevScanFetch. */
-   const size_t seg = nbytes < s->seg_bytes ? nbytes : s->seg_bytes;
-   size_t want_lines = s->cap_lines, want_hl = s->cap_hitlines, want_rec = s->cap_records;
-   if (!s->user_reserved) {
-      const size_t guess = (options & SEEQDEV_SINGLELINE) ? 1 : seg / 32 + 1024;
-      if (guess > want_lines) want_lines = guess;
-      if (want_lines / (size_t)hl_div + 1024 > want_hl) want_hl = want_lines / (size_t)hl_div + 1024;
-      /* the one-pass kernels cut the hit-line workspace into one slice per wave (<= 8 192 of them): room for 64
-         entries each, or the first scan with a hit always costs a second pass */
-      if (!(options & SEEQDEV_SINGLELINE) && want_hl < (size_t)8192 * 64) want_hl = (size_t)8192 * 64;
-      if (want_hl > want_rec) want_rec = want_hl;
-   }
-   if (reserve_impl(s, nbytes ? nbytes : 1, want_lines, want_hl, want_rec)) return -1;
+   s->fallback.age();
+   /* The optimistic workspace: what is too small is detected on the device and fixed by a re-run (rerun_next). */
+   const RerunCaps w = seeq_first_reservation(nbytes < s->seg_bytes ? nbytes : s->seg_bytes, (options & SEEQDEV_SINGLELINE) != 0, hl_div,
+                                              {s->cap_lines, s->cap_hitlines, s->cap_records}, s->user_reserved);
+   if (reserve_impl(s, nbytes ? nbytes : 1, w.lines, w.hitlines, w.records)) return -1;
    /* Average line length (tile sizing of the fused kernel): caller's hint, else a 64 KiB sample. */
    if (s->line_hint > 0) {
       s->avg_line = s->line_hint;
@@ -2059,8 +2045,23 @@ static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const voi
    return 0;
 }
 
-/* The capacity a re-run asks for where a workspace overflowed: what the device reported it needs, plus an eighth */
-static size_t grown(uint64_t need) { return (size_t)need + (size_t)(need >> 3) + 64; }
+/* What follows run number `run` of the context's scan, given its counters (per, npat: those of the patterns of a one-walk multi scan) --
+   the policy is seeq_rerun.h's.  0: the counters are the result; 1: run again -- the fall-back flags are set, the workspace is reserved;
+   2: not one walk after all (multi only); -1: error. */
+static int rerun_next(seeqdev_scan *s, int run, const Counters &u, const Counters *per = NULL, int npat = 0)
+{
+   const RerunStep d = seeq_rerun_decide(run, {s->cap_lines, s->cap_hitlines, s->cap_records}, u, per, npat);
+   s->fallback.note(d.note);
+   if (d.verdict == RERUN_DONE) return 0;
+   if (d.verdict == RERUN_NOT_ONE_WALK) return 2;
+   if (d.verdict == RERUN_AGAIN) return reserve_impl(s, s->nbytes, d.cap.lines, d.cap.hitlines, d.cap.records) ? -1 : 1;
+   const bool bad = d.verdict == RERUN_BAD_ENTRY;      /* (else: the last run the policy allows came back void too) */
+   snprintf(g_last_error, sizeof g_last_error, "%s", bad ? "internal inconsistency in the hit list (k_stream_bounds)" : "workspace did not converge");
+   errno = bad ? EIO : ENOMEM;
+   return -1;
+}
+
+static seeqdev_counts_t counts_of(const Counters &h) { return {h.lines, h.matchlines, h.hits, h.records, h.headers}; }
 
 /* SEEQDEV_FASTQ: the filter of seeq_fastq.h over the first n records of `in` (with their line offsets, or NULL) into the context's
    scratch arrays, on its stream; the filter's counters follow to h_fqcnt.  Asynchronous; n > 0. */
@@ -2132,22 +2133,16 @@ extern "C" int seeqdevScanFetch(seeqdev_scan_t *s, seeqdev_counts_t *counts)
    seeqerr = 0;
    if (!s || !s->ran) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
-   /* Overflows surface one stage at a time (lines, hit lines, records, then k_stream's fall-backs): up to six
-      re-runs, and the result of the last one is checked too. */
-   for (int attempt = 0; attempt < 8; attempt++) {
+   for (int run = 0;; run++) {
       HIP_TRY(hipStreamSynchronize(s->stream), EIO);
       const Counters h = *s->h_cnt;
-      if (!h.overflow) {
+      const int next = rerun_next(s, run, h);
+      if (next < 0) return -1;
+      if (next == 0) {
          if (s->fastq) {
             if (!s->fq_done && fastq_finish(s, h)) return -1;
             s->fq_done = true;
-         } else {
-            s->counts.nlines = h.lines;
-            s->counts.nmatchlines = h.matchlines;
-            s->counts.nhits = h.hits;
-            s->counts.nrecords = h.records;
-            s->counts.nheaders = h.headers;
-         }
+         } else s->counts = counts_of(h);
          if (counts) *counts = s->counts;
          for (int i = 0; i < 4; i++) s->acc_ms[i] = 0.f;
          s->fwd_ms_avg = 0.f;
@@ -2178,30 +2173,8 @@ extern "C" int seeqdevScanFetch(seeqdev_scan_t *s, seeqdev_counts_t *counts)
          if (s->prof && s->have_h2d_ev) (void)hipEventElapsedTime(&s->h2d_ms, s->ev_h2d[0], s->ev_h2d[1]);
          return 0;
       }
-      /* Grow to what the device reported (plus slack for the parts it could not see) and re-run. */
-      size_t nl = s->cap_lines, nhl = s->cap_hitlines, nrec = s->cap_records;
-      if (h.overflow & OVF_LINES) nl = grown(h.need_lines);
-      if (h.overflow & OVF_HITLINES) nhl = grown(h.need_hitlines);
-      if (h.overflow & OVF_BAD_ENTRY) {
-         snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the hit list (k_stream_bounds)");
-         errno = EIO;
-         return -1;
-      }
-      if (h.overflow & OVF_NO_STREAM) s->no_stream = true;
-      if (h.overflow & OVF_NONDNA) s->no_stream_nd = true;
-      if (h.overflow & OVF_LONG_LINES) s->force_ll = true;
-      if (h.overflow & OVF_SEAM) s->no_window = true;        /* a line with candidates on both sides of a segment seam */
-      if (h.overflow & OVF_LEADER) s->no_leaders = true;     /* a leader's fresh start inside the walk before it */
-      if (h.overflow & OVF_FALLBACK) s->fallback_ttl = 32;
-      if (h.overflow & OVF_RECORDS) nrec = grown(h.need_records);     /* (need_records keeps counting after the overflow: the total of this run) */
-      if ((h.overflow & OVF_LINES) && nhl < nl / 8) nhl = nl / 8 + 64;
-      if (attempt == 7) break;
-      if (reserve_impl(s, s->nbytes, nl, nhl, nrec)) return -1;
       if (dispatch_run(s)) return -1;
    }
-   snprintf(g_last_error, sizeof g_last_error, "workspace did not converge");
-   errno = ENOMEM;
-   return -1;
 }
 
 extern "C" const seeqdev_hit_t *seeqdevScanRecordsDevice(const seeqdev_scan_t *s) { return s ? s->records : NULL; }
@@ -2251,14 +2224,9 @@ extern "C" int seeqdevScanPacked(seeqdev_scan_t *s, const seeqdev_pattern_t *pat
    s->ran = false;
    s->is_packed = true;
    s->packed = *batch;
-   /* optimistic workspace: one read in eight is a candidate (grown by the re-run of seeqdevScanFetch when it is not) */
-   const size_t seg = batch->nreads < s->pk_seg_reads ? (size_t)batch->nreads : s->pk_seg_reads;
-   size_t want_hl = s->cap_hitlines, want_rec = s->cap_records;
-   if (!s->user_reserved) {
-      if (seg / 8 + 1024 > want_hl) want_hl = seg / 8 + 1024;
-      if (want_hl > want_rec) want_rec = want_hl;
-   }
-   if (reserve_impl(s, 1, 0, want_hl, want_rec)) return -1;
+   const RerunCaps w = seeq_first_reservation_packed(batch->nreads < s->pk_seg_reads ? (size_t)batch->nreads : s->pk_seg_reads,
+                                                     {s->cap_lines, s->cap_hitlines, s->cap_records}, s->user_reserved);
+   if (reserve_impl(s, 1, w.lines, w.hitlines, w.records)) return -1;
    if (dispatch_run(s)) return -1;
    s->ran = true;
    return 0;
@@ -2543,10 +2511,10 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
       if (e != hipSuccess) return hip_fail(e, "hipMemcpy(EQ tables)", EIO);
       mp->eq_options = options;
    }
-   if (scan_setup(s, &mp->upat, d_text, nbytes, options, want, 2)) return -1;
+   if (scan_setup(s, &mp->upat, d_text, nbytes, options, want, SEEQ_HL_DIV_MULTI)) return -1;
    s->multi_active = true;
    int rc = -1;
-   for (int attempt = 0; attempt < 8; attempt++) {
+   for (int run = 0;; run++) {
       if (multi_ws_ensure(s, npat)) break;
       if (hipMemsetAsync(s->d_mcnt, 0, SEEQ_MULTI_MAX * sizeof(Counters), s->stream) != hipSuccess) { errno = EIO; break; }
       const int r = dispatch_run(s);
@@ -2554,17 +2522,10 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
       if (r) break;
       if (hipMemcpyAsync(s->h_mcnt, s->d_mcnt, (size_t)npat * sizeof(Counters), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
           hipStreamSynchronize(s->stream) != hipSuccess) { errno = EIO; break; }
-      const Counters u = *s->h_cnt;
-      uint32_t povf = 0, need_hl = 0;
-      uint64_t need_rec = 0;
-      for (int k = 0; k < npat; k++) {
-         povf |= s->h_mcnt[k].overflow;
-         if (s->h_mcnt[k].need_hitlines > need_hl) need_hl = s->h_mcnt[k].need_hitlines;
-         if (s->h_mcnt[k].need_records > need_rec) need_rec = s->h_mcnt[k].need_records;
-      }
-      if (u.overflow & OVF_BAD_ENTRY) { snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the hit list (k_stream_bounds)"); errno = EIO; break; }
-      if (u.overflow & (OVF_NO_STREAM | OVF_NONDNA | OVF_LONG_LINES)) { rc = 1; break; }          /* not k_pair's text after all: a scan per pattern */
-      if (!u.overflow && !povf) {
+      const int next = rerun_next(s, run, *s->h_cnt, s->h_mcnt, npat);
+      if (next == 1) continue;
+      if (next == 2) rc = 1;                                /* not k_pair's text after all: a scan per pattern */
+      if (next == 0) {
          /* results: counts, then every pattern's records from its region */
          const uint64_t capR = s->cap_records / (uint64_t)npat;
          if (demux) {
@@ -2581,8 +2542,7 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
          }
          for (int k = 0; k < npat && rc == 0; k++) {
             const Counters &h = s->h_mcnt[k];
-            seeqdev_counts_t &o = s->multi_cnt[k];
-            o.nlines = h.lines; o.nmatchlines = h.matchlines; o.nhits = h.hits; o.nrecords = h.records; o.nheaders = h.headers;
+            s->multi_cnt[k] = counts_of(h);
             s->multi_first[k] = s->multi_nrec;
             const size_t n = want == SEEQDEV_WANT_RECORDS ? (size_t)h.records : 0;
             if (n) {
@@ -2590,21 +2550,12 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
                if (hipMemcpyAsync(s->multi_rec + s->multi_nrec, s->records + (uint64_t)k * capR, n * sizeof(seeqdev_hit_t), hipMemcpyDeviceToHost, s->stream) != hipSuccess) { errno = EIO; rc = -1; break; }
                s->multi_nrec += n;
             }
-            if (counts) counts[k] = o;
+            if (counts) counts[k] = s->multi_cnt[k];
          }
          if (rc == 0 && hipStreamSynchronize(s->stream) != hipSuccess) { errno = EIO; rc = -1; }
          if (rc == 0) { s->multi_first[npat] = s->multi_nrec; s->multi_n = npat; s->last_multi = 1; }
-         break;
       }
-      size_t nl = s->cap_lines, nhl = s->cap_hitlines, nrec = s->cap_records;
-      if (u.overflow & OVF_LINES) nl = grown(u.need_lines);
-      if (u.overflow & OVF_HITLINES) nhl = grown(u.need_hitlines);
-      if (u.overflow & OVF_SEAM) { s->no_window = true; s->fallback_ttl = 32; }
-      if (povf & OVF_HITLINES) { const size_t w = grown(need_hl) * (size_t)npat; if (w > nhl) nhl = w; }
-      if (povf & OVF_RECORDS) { const size_t w = grown(need_rec) * (size_t)npat; if (w > nrec) nrec = w; }
-      if ((u.overflow & OVF_LINES) && nhl < nl / 2) nhl = nl / 2 + 64;
-      if (attempt == 7) { snprintf(g_last_error, sizeof g_last_error, "workspace did not converge"); errno = ENOMEM; break; }
-      if (reserve_impl(s, s->nbytes, nl, nhl, nrec)) break;
+      break;
    }
    s->multi_active = false;
    s->ran = false;                                         /* (seeqdevScanFetch has nothing to fetch: the multi scan is complete) */

@@ -1,17 +1,17 @@
 /*
  * seeq_types.h -- the argument blocks every kernel of the scan shares (seeq_device.hip, seeq_verify.hip):
- * the per-run counters in HBM and the per-segment arguments of the post-pass.
+ * the per-run counters in HBM and the per-segment arguments of the post-pass.  The counters and their overflow bits are plain
+ * C++ -- the host's re-run policy (seeq_rerun.h) reads them, on the CPU too --; the arguments of the post-pass need HIP's types.
  */
 #ifndef SEEQ_TYPES_H_
 #define SEEQ_TYPES_H_
 
 #include <stdint.h>
-#include "seeq_amd.h"
 
 /* ========================================================================== */
 /* Device-side bookkeeping                                                    */
 /* ========================================================================== */
-/* Counters.overflow: why a run is void.  The first three ask seeqdevScanFetch for more workspace, the fall-back bits for other kernels. */
+/* Counters.overflow: why a run is void.  The first three ask the re-run policy (seeq_rerun.h) for more workspace, the fall-back bits for other kernels. */
 enum : uint32_t {
    OVF_LINES      = 1u,      /* per-line workspace too small */
    OVF_HITLINES   = 2u,      /* hit-line workspace too small */
@@ -52,6 +52,9 @@ struct Counters {
    uint32_t pad4[2];
    uint64_t emit_base;
 };
+
+#if defined(__HIPCC__)
+#include "seeq_amd.h"
 
 struct ScanArgs {
    const uint8_t *text;      /* whole buffer */
@@ -105,7 +108,6 @@ struct ScanArgs {
 };
 
 /* per hit-list entry: records of the segment before it (see nh_sum) */
-#if defined(__HIPCC__)
 __device__ __forceinline__ uint32_t nh_at(const ScanArgs &a, uint32_t k) { return a.nh[k] + (a.nh_sum ? a.nh_sum[k >> 8] : 0u); }
 /* what seeqdevScanCopyOffsets reports for a record of line number `line` whose text starts at byte `off` of the scanned buffer */
 __device__ __forceinline__ uint64_t rec_off_of(const ScanArgs &a, uint64_t off, uint32_t line) { return a.rec_pitch ? (uint64_t)(line - 1u) * a.rec_pitch : off; }

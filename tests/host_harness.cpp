@@ -550,3 +550,43 @@ extern "C" int harness_ws_script(long refuse_at, long long *rows, int max_rows)
    }
    return ns;
 }
+
+// ---- the re-run policy of a scan context (seeq_amd/csrc/seeq_rerun.h): the same pure functions seeqdevScanFetch and the one-walk multi
+//      scan call after every run -- counters in, verdict / capacities / fall-back bits out.
+//      harness_rerun_decide: cap[3] = lines, hit lines, records; npat > 0: one walk for npat patterns, per = npat rows of {overflow,
+//      need_hitlines, need_records}.  out[5] = verdict (RerunVerdict), the three capacities to reserve, the bits to note.
+//      harness_fallback: a script over one RerunFallback -- op 0 = age(), anything else = note(op); per op a row of 7: bits, ttl, no_stream,
+//      no_stream_nd, force_ll, no_window, no_leaders.
+//      harness_first_reservation: what a scan asks for before its first run (packed: seg in reads) -> out[3]. ----
+#include "../seeq_amd/csrc/seeq_rerun.h"
+
+extern "C" void harness_rerun_decide(int run, const uint64_t *cap, uint32_t overflow, uint32_t need_lines, uint32_t need_hitlines, uint64_t need_records,
+                                     int npat, const uint64_t *per, uint64_t *out)
+{
+   Counters u;
+   std::memset(&u, 0, sizeof u);
+   u.overflow = overflow; u.need_lines = need_lines; u.need_hitlines = need_hitlines; u.need_records = need_records;
+   std::vector<Counters> pc((size_t)(npat > 0 ? npat : 1));
+   std::memset(pc.data(), 0, pc.size() * sizeof(Counters));
+   for (int k = 0; k < npat; k++) { pc[k].overflow = (uint32_t)per[3 * k]; pc[k].need_hitlines = (uint32_t)per[3 * k + 1]; pc[k].need_records = per[3 * k + 2]; }
+   const RerunStep d = seeq_rerun_decide(run, {(size_t)cap[0], (size_t)cap[1], (size_t)cap[2]}, u, npat > 0 ? pc.data() : NULL, npat);
+   out[0] = (uint64_t)d.verdict; out[1] = d.cap.lines; out[2] = d.cap.hitlines; out[3] = d.cap.records; out[4] = d.note;
+}
+
+extern "C" void harness_fallback(const uint32_t *ops, int nops, int *rows)
+{
+   RerunFallback f = {0, 0};
+   for (int i = 0; i < nops; i++) {
+      if (ops[i]) f.note(ops[i]); else f.age();
+      const int v[7] = {(int)f.bits, f.ttl, f.no_stream(), f.no_stream_nd(), f.force_ll(), f.no_window(), f.no_leaders()};
+      for (int j = 0; j < 7; j++) rows[7 * i + j] = v[j];
+   }
+}
+
+extern "C" void harness_first_reservation(int packed, uint64_t seg, int singleline, int hl_div, const uint64_t *cap, int user_reserved, uint64_t *out)
+{
+   const RerunCaps c = {(size_t)cap[0], (size_t)cap[1], (size_t)cap[2]};
+   const RerunCaps w = packed ? seeq_first_reservation_packed((size_t)seg, c, user_reserved != 0)
+                              : seeq_first_reservation((size_t)seg, singleline != 0, hl_div, c, user_reserved != 0);
+   out[0] = w.lines; out[1] = w.hitlines; out[2] = w.records;
+}

@@ -257,6 +257,35 @@ def test_packed_record_offsets_are_those_of_the_ascii_form(gpu, capi):
     sc.close(); pat.close()
 
 
+def test_packed_tiny_reserve_reruns_equal_the_ascii_scan(gpu, capi):
+    """The packed scan's re-runs through seeqdevScanFetch: a context the caller sized absurdly small (its reservation is trusted, so the
+    hit-list and the record workspace both overflow and grow from what the device reports) against the ASCII scan of the same reads on a
+    fresh context -- counts, records and record offsets."""
+    import torch
+    from seeq_amd import device as dev
+    n, L = 6000, 150
+    pattern, tau = "GATGTAGCGCGATTAGCCTG", 3
+    stream = torch.cuda.current_stream().cuda_stream
+    text = torch.empty(n * (L + 1), dtype=torch.uint8, device="cuda:0")
+    dev.synth_reads(text.data_ptr(), 0, n, L, pattern, tau, stream=stream)
+    db = torch.empty(n * ((L + 3) // 4), dtype=torch.uint8, device="cuda:0"); dn = torch.empty(n * ((L + 7) // 8), dtype=torch.uint8, device="cuda:0")
+    dev.pack_reads_device(text.data_ptr(), n, L, db.data_ptr(), dn.data_ptr(), stream=stream)
+    pat = dev.Pattern(pattern, tau)
+    for mo in (SQ_BEST, SQ_ALL):
+        fresh = dev.Scanner(stream)
+        fresh.run(pat, text.data_ptr(), text.numel(), mo, dev.WANT_RECORDS)
+        a = fresh.fetch(); ra = fresh.records(a["nrecords"]); oa = fresh.record_offsets(a["nrecords"])
+        sc = dev.Scanner(stream)
+        sc.reserve(0, 10, 2, 1)                 # absurdly small: OVF_HITLINES, then OVF_RECORDS
+        sc.run_packed(pat, db.data_ptr(), dn.data_ptr(), n, L, options=mo, want=dev.WANT_RECORDS)
+        b = sc.fetch(); rb = sc.records(b["nrecords"]); ob = sc.record_offsets(b["nrecords"])
+        assert sc.last_kernel() == "k_packed" and a == b and a["nlines"] == n and a["nrecords"] > n // 100, (mo, a, b)
+        assert np.array_equal(ra, rb), mo
+        assert np.array_equal(oa, ob), mo
+        fresh.close(); sc.close()
+    pat.close()
+
+
 def _packed_fuzz(dev, torch, oracle, seed, ncases, nreads=1500):
     """Random patterns (classes, N, 4 .. 44 positions, distance 0 .. 5), random read lengths, reads with planted mutated copies, N and lower
     case: the packed scan against the oracle for every match option and both counts.  Returns how many cases walked the quad table."""

@@ -853,3 +853,195 @@ def test_workspace_growth_is_grouped_and_every_refusal_leaves_it_whole(harness):
         else:
             assert later[0]["set_held"] == later[0]["members"], (n, later[0])
         assert {q["g"]: q["cap"] for q in rows if q["kind"] == GROW} == final_cap, n
+
+
+# ---- the re-run policy (seeq_amd/csrc/seeq_rerun.h) over host_harness.cpp.  Every expected number below is written out from the arithmetic the
+#      host driver carried before the policy had a header of its own: a grown capacity is need + need // 8 + 64. ----
+OVF_LINES, OVF_HITLINES, OVF_RECORDS, OVF_NO_STREAM, OVF_NONDNA, OVF_LONG_LINES, OVF_BAD_ENTRY, OVF_SEAM, OVF_LEADER = 1, 2, 4, 8, 16, 32, 64, 128, 256
+DONE, AGAIN, BAD_ENTRY, NOT_ONE_WALK, NO_CONVERGENCE = range(5)
+MAX_RUNS = 8
+
+
+def _decide(H, cap, overflow, need=(0, 0, 0), per=None, run=0):
+    """-> (verdict, (lines, hit lines, records) to reserve, bits to note)"""
+    import ctypes as C
+    H.harness_rerun_decide.restype = None
+    H.harness_rerun_decide.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+    c = np.array(cap, dtype=np.uint64)
+    p = np.array(per if per else [[0, 0, 0]], dtype=np.uint64).reshape(-1, 3)
+    out = np.zeros(5, dtype=np.uint64)
+    H.harness_rerun_decide(run, c.ctypes.data, overflow, need[0], need[1], need[2], len(per) if per else 0, p.ctypes.data, out.ctypes.data)
+    return int(out[0]), tuple(int(v) for v in out[1:4]), int(out[4])
+
+
+def _fallback(H, ops):
+    """ops: 0 = age(), else note(op) -> per op a dict of the state after it"""
+    import ctypes as C
+    H.harness_fallback.restype = None
+    H.harness_fallback.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    o = np.array(ops, dtype=np.uint32)
+    rows = np.zeros((len(ops), 7), dtype=np.int32)
+    H.harness_fallback(o.ctypes.data, len(ops), rows.ctypes.data)
+    return [dict(zip(("bits", "ttl", "no_stream", "no_stream_nd", "force_ll", "no_window", "no_leaders"), (int(v) for v in r))) for r in rows]
+
+
+def test_rerun_decisions_of_a_single_pattern_scan(harness):
+    """What seeqdevScanFetch does with the counters of a void run: a workspace whose bit is set grows to need + need / 8 + 64, a line overflow
+    brings the hit lines to at least lines / 8 + 64, a fall-back bit is noted and leaves the capacities alone, a bad entry fails the scan."""
+    H = harness
+    cap = (10, 2, 1)
+    assert _decide(H, cap, 0) == (DONE, cap, 0)
+    assert _decide(H, cap, 0, need=(1000, 5000, 100000)) == (DONE, cap, 0)                       # needs without their bit say nothing
+    need = (1000, 5000, 100000)
+    assert _decide(H, cap, OVF_LINES, need) == (AGAIN, (1189, 212, 1), 0)                        # 1000 + 125 + 64; 1189 // 8 + 64
+    assert _decide(H, cap, OVF_HITLINES, need) == (AGAIN, (10, 5689, 1), 0)                      # 5000 + 625 + 64
+    assert _decide(H, cap, OVF_RECORDS, need) == (AGAIN, (10, 2, 112564), 0)                     # 100000 + 12500 + 64
+    assert _decide(H, cap, OVF_LINES | OVF_HITLINES | OVF_RECORDS, need) == (AGAIN, (1189, 5689, 112564), 0)
+    # hit lines after a line overflow: the reported need where it is the larger (100 + 12 + 64 = 176 >= 1189 // 8 = 148), else lines // 8 + 64
+    assert _decide(H, cap, OVF_LINES | OVF_HITLINES, (1000, 100, 0)) == (AGAIN, (1189, 176, 1), 0)
+    assert _decide(H, cap, OVF_LINES | OVF_HITLINES, (1000, 10, 0)) == (AGAIN, (1189, 212, 1), 0)     # 10 + 1 + 64 = 75 < 148
+    assert _decide(H, (10, 5000, 1), OVF_LINES, need) == (AGAIN, (1189, 5000, 1), 0)
+    assert _decide(H, cap, OVF_RECORDS, (0, 0, 5_000_000_000)) == (AGAIN, (10, 2, 5_625_000_064), 0)   # the record total is 64 bits wide
+    # the fall-back bits: exactly the matching flag, 32 scans to live, the capacities as they were
+    flag_of = {OVF_NO_STREAM: "no_stream", OVF_NONDNA: "no_stream_nd", OVF_LONG_LINES: "force_ll", OVF_SEAM: "no_window", OVF_LEADER: "no_leaders"}
+    for bit, name in flag_of.items():
+        assert _decide(H, cap, bit, need) == (AGAIN, cap, bit)
+        st = _fallback(H, [bit])[0]
+        assert st == dict({n: int(n == name) for n in flag_of.values()}, bits=bit, ttl=32), (bit, st)
+    every = sum(flag_of)
+    assert every == 0x1B8
+    assert _decide(H, cap, every, need) == (AGAIN, cap, every)
+    assert _fallback(H, [every])[0] == dict({n: 1 for n in flag_of.values()}, bits=every, ttl=32)
+    assert _decide(H, cap, every | OVF_HITLINES, need) == (AGAIN, (10, 5689, 1), every)
+    assert _fallback(H, [OVF_LINES | OVF_HITLINES | OVF_RECORDS | OVF_BAD_ENTRY])[0]["bits"] == 0 # only fall-back bits are remembered
+    # a bad entry fails the scan whatever else is set, and nothing of that run is noted
+    for other in (0, OVF_LINES, OVF_RECORDS | OVF_SEAM, every | 7):
+        v, _, note = _decide(H, cap, OVF_BAD_ENTRY | other, need)
+        assert (v, note) == (BAD_ENTRY, 0), other
+
+
+def test_rerun_decisions_of_a_one_walk_multi_scan(harness):
+    """The same function in the mode of multi_one_pass: the patterns' largest needs count npat times (their regions share the arrays) and are taken
+    only above what the walk's own counters ask for, hit lines after a line overflow are lines / 2 + 64, only the seam flag is remembered, and text
+    that is not k_pair's ends the walk with nothing noted."""
+    H = harness
+    cap = (10, 2, 1)
+    quiet = [[0, 0, 0]] * 4
+    assert _decide(H, cap, 0, per=quiet) == (DONE, cap, 0)
+    per = [[OVF_HITLINES, 300, 0], [0, 100, 0], [OVF_RECORDS, 0, 7000], [OVF_RECORDS, 50, 9000]]
+    # (300 + 37 + 64) * 4 = 1604; (9000 + 1125 + 64) * 4 = 40756
+    assert _decide(H, cap, 0, per=per) == (AGAIN, (10, 1604, 40756), 0)
+    assert _decide(H, cap, 0, per=[[OVF_HITLINES, 300, 9000]] + quiet[1:]) == (AGAIN, (10, 1604, 1), 0)      # a need without its bit says nothing
+    assert _decide(H, cap, OVF_HITLINES, (0, 4000, 0), per=per) == (AGAIN, (10, 4564, 40756), 0)             # the walk's 4000 + 500 + 64 is larger
+    assert _decide(H, cap, OVF_HITLINES, (0, 100, 0), per=per) == (AGAIN, (10, 1604, 40756), 0)              # ... 100 + 12 + 64 is not
+    assert _decide(H, (10, 2, 50000), 0, per=per) == (AGAIN, (10, 1604, 50000), 0)                            # nor is a region sum below the capacity
+    assert _decide(H, cap, OVF_LINES, (1000, 0, 0), per=quiet) == (AGAIN, (1189, 658, 1), 0)                  # 1189 // 2 + 64
+    assert _decide(H, cap, OVF_LINES, (1000, 0, 0), per=per) == (AGAIN, (1189, 1604, 40756), 0)
+    assert _decide(H, cap, OVF_RECORDS, (0, 0, 100000), per=quiet) == (AGAIN, cap, 0)         # records are the patterns' business: the walk's bit grows nothing
+    assert _decide(H, cap, OVF_SEAM, per=quiet) == (AGAIN, cap, OVF_SEAM)
+    assert _fallback(H, [OVF_SEAM])[0] == dict(bits=OVF_SEAM, ttl=32, no_stream=0, no_stream_nd=0, force_ll=0, no_window=1, no_leaders=0)
+    assert _decide(H, cap, OVF_SEAM | OVF_LEADER | OVF_HITLINES, (0, 4000, 0), per=per) == (AGAIN, (10, 4564, 40756), OVF_SEAM)
+    for bit in (OVF_NO_STREAM, OVF_NONDNA, OVF_LONG_LINES):
+        for other in (0, OVF_SEAM, OVF_LINES | OVF_HITLINES):
+            assert _decide(H, cap, bit | other, (1000, 4000, 0), per=per) == (NOT_ONE_WALK, cap, 0), (bit, other)
+        assert _decide(H, cap, bit | OVF_BAD_ENTRY, per=quiet)[0] == BAD_ENTRY
+
+
+def test_rerun_loop_converges_against_a_scripted_device(harness):
+    """The loop both callers run, against a fake device that reports as the real one does -- one stage per run: lines, then hit lines, then records,
+    then a fall-back bit -- until the capacities reach fixed needs: done within the eight runs the policy allows, every capacity at least its need and
+    never smaller than before.  A device that never clears gets the non-convergence verdict on the eighth run, not earlier and not later."""
+    H = harness
+    # (needs, one walk for four patterns?, first capacities, runs: a one-walk scan's lines / 2 + 64 hit lines cover the second stage)
+    for needs, per_walk, first, want_runs in (((200000, 90000, 3000000), False, (10, 2, 1), 5), ((200000, 90000, 3000000), True, (10, 2, 1), 4),
+                                              ((29000, 600000, 700000), False, (29336, 524288, 524288), 4), ((5, 1, 1), False, (10, 2, 1), 2)):
+        cap, noted, runs, fb = first, 0, 0, OVF_SEAM if per_walk else OVF_LONG_LINES
+        quiet = [[0, 0, 0]] * 4
+        while True:
+            assert runs < MAX_RUNS
+            # the fake device: the first stage that does not fit; a one-walk scan reports hit lines and records per pattern (a quarter each)
+            ovf, need, per = 0, (0, 0, 0), quiet if per_walk else None
+            if cap[0] < needs[0]:
+                ovf, need = OVF_LINES, (needs[0], 0, 0)
+            elif cap[1] < needs[1]:
+                if per_walk:
+                    per = [[OVF_HITLINES, needs[1] // 4, 0]] + quiet[1:]
+                else:
+                    ovf, need = OVF_HITLINES, (0, needs[1], 0)
+            elif cap[2] < needs[2]:
+                if per_walk:
+                    per = quiet[:3] + [[OVF_RECORDS, 0, needs[2] // 4]]
+                else:
+                    ovf, need = OVF_RECORDS, (0, 0, needs[2])
+            elif not noted & fb:
+                ovf = fb
+            verdict, nxt, note = _decide(H, cap, ovf, need, per=per, run=runs)
+            runs += 1
+            noted |= note
+            if verdict == DONE:
+                break
+            assert verdict == AGAIN, (needs, runs, verdict)
+            assert all(n >= c for n, c in zip(nxt, cap)), (cap, nxt)
+            cap = nxt
+        assert all(c >= n for c, n in zip(cap, needs)) and noted == fb, (cap, needs, noted)
+        assert runs == want_runs, (needs, runs)
+    # eight stages, none of which clears: whatever was asked for, the next run needs more
+    stages = (OVF_LINES, OVF_HITLINES, OVF_RECORDS, OVF_NO_STREAM, OVF_NONDNA, OVF_LONG_LINES, OVF_SEAM, OVF_LEADER | OVF_RECORDS)
+    for per in (None, [[OVF_HITLINES | OVF_RECORDS, 10**6, 10**7]] * 4):
+        cap, verdicts = (10, 2, 1), []
+        for run, ovf in enumerate(stages):
+            if per:
+                ovf &= ~(OVF_NO_STREAM | OVF_NONDNA | OVF_LONG_LINES)
+            verdict, nxt, _ = _decide(H, cap, ovf, (2 * cap[0], 2 * cap[1], 2 * cap[2]), per=per, run=run)
+            verdicts.append(verdict)
+            assert all(n >= c for n, c in zip(nxt, cap))
+            cap = nxt
+        assert verdicts == [AGAIN] * 7 + [NO_CONVERGENCE]
+    assert _decide(H, (10, 2, 1), 0, run=7) == (DONE, (10, 2, 1), 0)                             # the result of the eighth run counts
+
+
+def test_fallback_flags_age_out_after_32_scans(harness):
+    """A noted flag holds for the 31 scans that follow and is gone on the 32nd; noting again restarts the count; without a flag nothing is counted."""
+    H = harness
+    st = _fallback(H, [OVF_SEAM] + [0] * 40)
+    assert [s["no_window"] for s in st] == [1] * 32 + [0] * 9
+    assert [s["ttl"] for s in st[:33]] == list(range(32, -1, -1)) and all(s["ttl"] == 0 and s["bits"] == 0 for s in st[32:])
+    st = _fallback(H, [OVF_SEAM] + [0] * 10 + [OVF_LEADER] + [0] * 32)
+    assert st[10]["ttl"] == 22 and st[11] == dict(bits=OVF_SEAM | OVF_LEADER, ttl=32, no_stream=0, no_stream_nd=0, force_ll=0, no_window=1, no_leaders=1)
+    assert all(s["bits"] == OVF_SEAM | OVF_LEADER for s in st[11:43]) and st[42]["ttl"] == 1
+    assert st[43]["bits"] == 0                                                                   # both flags go together
+    st = _fallback(H, [OVF_LINES, 0, 0, OVF_LONG_LINES, 0])                                       # a workspace bit is no flag and restarts nothing
+    assert [(s["bits"], s["ttl"]) for s in st] == [(0, 0), (0, 0), (0, 0), (OVF_LONG_LINES, 32), (OVF_LONG_LINES, 31)]
+
+
+def test_first_reservation_of_ascii_and_packed_scans(harness):
+    """What a scan reserves before its first run: seg / 32 + 1024 lines, one hit line in hl_div (+ 1024), at least 8192 * 64 hit lines for the
+    one-pass kernels, records at least hit lines; a packed batch: one read in eight (+ 1024).  Never less than the context has, and exactly what it
+    has where the caller sized the workspace."""
+    import ctypes as C
+    H = harness
+    H.harness_first_reservation.restype = None
+    H.harness_first_reservation.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+
+    def first(seg, hl_div=8, cap=(0, 0, 0), packed=0, single=0, user=0):
+        c, out = np.array(cap, dtype=np.uint64), np.zeros(3, dtype=np.uint64)
+        H.harness_first_reservation(packed, seg, single, hl_div, c.ctypes.data, user, out.ctypes.data)
+        return tuple(int(v) for v in out)
+    reads = 6000 * 151                                                       # 906 000 bytes: 28 312 + 1024 lines, 3667 + 1024 hit lines -> the floor
+    assert first(reads) == (29336, 524288, 524288)
+    assert first(reads, hl_div=2) == (29336, 524288, 524288)                 # 14 668 + 1024: the floor still
+    seg = 0xF0000000                                                         # a 3.75 GiB segment: 125 829 120 + 1024 lines
+    assert first(seg) == (125830144, 15729792, 15729792)                     # 15 728 768 + 1024
+    assert first(seg, hl_div=2) == (125830144, 62916096, 62916096)           # 62 915 072 + 1024
+    assert first(seg, single=1) == (1, 1024, 1024)                           # SEEQDEV_SINGLELINE: one line, no floor
+    assert first(seg, single=1, cap=(7, 5000, 3)) == (7, 5000, 5000)
+    # a context that holds more keeps it; records follow the hit lines up
+    assert first(reads, cap=(50000, 10, 10)) == (50000, 524288, 524288)      # 6250 + 1024 from the lines it has
+    assert first(seg, cap=(10, 20000000, 30000000)) == (125830144, 20000000, 30000000)
+    assert first(6000, packed=1) == (0, 1774, 1774)                          # 750 + 1024
+    assert first(1 << 26, packed=1) == (0, 8389632, 8389632)                 # the largest packed segment: 2^23 + 1024
+    assert first(6000, packed=1, cap=(10, 2, 1)) == (10, 1774, 1774)
+    assert first(6000, packed=1, cap=(10, 5000, 9000)) == (10, 5000, 9000)
+    for cap in ((10, 2, 1), (0, 0, 0), (125830144, 7, 3)):
+        for kw in (dict(), dict(hl_div=2), dict(single=1), dict(packed=1)):
+            assert first(reads, cap=cap, user=1, **kw) == cap, (cap, kw)
