@@ -1,6 +1,6 @@
 /*
- * seeq_device.hip -- HIP kernels and the device-level C-ABI (include/seeq_amd.h)
- * of seeq-mi355x.  Written for gfx950 (MI355X, CDNA4): 64-wide wavefronts,
+ * seeq_device.hip -- the device-level C-ABI (include/seeq_amd.h) of seeq-mi355x: ONE
+ * translation unit, the kernels and the drivers of the side entries in headers.  Written for gfx950 (MI355X, CDNA4): 64-wide wavefronts,
  * one text line per lane, wave ballots for per-line flags, LDS for the Peq and
  * class tables.  Integer/bitwise work only -- no MFMA.
  *
@@ -15,8 +15,14 @@
  *   K4  k_exact<W,COUNT>             (SQ_ALL / COUNTMATCH) hits per hit line, then scan
  *   K5  k_exact<W,EMIT>              acceptance rules + reverse start recovery -> records[]
  *
- * replacing the reference's per-line loop seeq.c:361-387 -> libseeq.c:171-352.
- * There is no host-side matcher: without a GPU every entry point fails.
+ * (the generic path: seeq_generic.h, seeq_scan.h; the one-pass kernels that serve most
+ * scans: seeq_pair.h, seeq_stream.h, seeq_direct.h) replacing the reference's per-line
+ * loop seeq.c:361-387 -> libseeq.c:171-352.  There is no host-side matcher: without a
+ * GPU every entry point fails.
+ *
+ * Here: plumbing, pattern handle, scan context, the segment and packed drivers, the scan
+ * entries.  The side entries are included where they belong in that order: seeq_synth.h,
+ * seeq_text_alloc.h, seeq_multi_host.h, seeq_demux_host.h, seeq_string.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -89,357 +95,8 @@ static constexpr uint32_t STREAM_CH_HOST = 128;    /* bytes per lane of k_stream
 static constexpr size_t MAX_FUSED_GRID = 16384;   /* upper bound of the waves (= hit slices) of a persistent scan grid */
 static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate the line length */
 
-/* ========================================================================== */
-/* Block-level helpers                                                        */
-/* ========================================================================== */
-/* 64-bit mask of newline positions among the 64 bytes this thread owns
- * (bytes seg_base + tile*TILE + tid*64 ...), restricted to positions q with
- * q < seg_base+seg_len and q + 1 < nbytes (a final '\n' starts no line). */
-__device__ __forceinline__ uint64_t thread_nl_mask(const ScanArgs &a, uint32_t tile)
-{
-   const uint64_t seg_off = (uint64_t)tile * TILE + (uint64_t)threadIdx.x * 64;
-   if (seg_off >= a.seg_len) return 0;
-   const uint64_t q0 = a.seg_base + seg_off;
-   uint64_t limit = a.seg_base + a.seg_len;                /* exclusive */
-   if (a.nbytes - 1 < limit) limit = a.nbytes - 1;         /* q + 1 < nbytes  (nbytes > 0 here) */
-   uint64_t mask = 0;
-   if (q0 + 64 <= limit && ((uintptr_t)(a.text + q0) & 15) == 0) {
-      const uint4 *p = reinterpret_cast<const uint4 *>(a.text + q0);
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-         const uint4 v = p[j];
-         const uint32_t f0 = nl_flags(v.x), f1 = nl_flags(v.y), f2 = nl_flags(v.z), f3 = nl_flags(v.w);
-         /* gather bit 7 of each byte into 4 consecutive bits */
-         const uint32_t b0 = ((f0 >> 7) * 0x00204081u >> 21) & 0xFu;
-         const uint32_t b1 = ((f1 >> 7) * 0x00204081u >> 21) & 0xFu;
-         const uint32_t b2 = ((f2 >> 7) * 0x00204081u >> 21) & 0xFu;
-         const uint32_t b3 = ((f3 >> 7) * 0x00204081u >> 21) & 0xFu;
-         const uint64_t m16 = b0 | (b1 << 4) | (b2 << 8) | (b3 << 12);
-         mask |= m16 << (16 * j);
-      }
-   } else {
-      for (int k = 0; k < 64; k++) {
-         const uint64_t q = q0 + k;
-         if (q < limit && a.text[q] == '\n') mask |= 1ull << k;
-      }
-   }
-   return mask;
-}
-
-/* ========================================================================== */
-/* K0: newline index                                                          */
-/* ========================================================================== */
-__global__ __launch_bounds__(WG) void k_nl_count(ScanArgs a)
-{
-   __shared__ uint32_t s_wave[4];
-   const uint64_t m = thread_nl_mask(a, blockIdx.x);
-   uint32_t tot;
-   block_excl_scan((uint32_t)__popcll(m), &tot, s_wave);
-   if (threadIdx.x == 0) a.tile_cnt[blockIdx.x] = tot;
-}
-
-/* After tile_cnt has been scanned in place (exclusive) and the total written
- * to cnt->seg_nlines: add the line that starts at byte 0 of the buffer. */
-__global__ void k_index_finalize(ScanArgs a)
-{
-   Counters *c = a.cnt;
-   uint32_t n = c->seg_nlines;
-   if (a.first_seg && a.nbytes > 0) n += 1;
-   if (n > a.cap_lines) {
-      atomicOr(&c->overflow, OVF_LINES);
-      if (n > c->need_lines) c->need_lines = n;
-      n = 0;                       /* later kernels of this segment do nothing */
-   } else if (n > c->need_lines) {
-      c->need_lines = n;
-   }
-   c->seg_nlines = n;
-   if (n && a.first_seg) a.line_start[0] = 0;
-}
-
-__global__ __launch_bounds__(WG) void k_nl_write(ScanArgs a)
-{
-   __shared__ uint32_t s_wave[4];
-   if (a.cnt->seg_nlines == 0) return;
-   uint64_t m = thread_nl_mask(a, blockIdx.x);
-   uint32_t tot;
-   uint32_t rank = block_excl_scan((uint32_t)__popcll(m), &tot, s_wave);
-   rank += a.tile_cnt[blockIdx.x] + (a.first_seg ? 1u : 0u);
-   const uint32_t off0 = blockIdx.x * TILE + threadIdx.x * 64 + 1;   /* start = newline position + 1 */
-   while (m) {
-      const int b = __builtin_ctzll(m);
-      m &= m - 1;
-      a.line_start[rank++] = off0 + (uint32_t)b;
-   }
-}
-
-/* ========================================================================== */
-/* Generic two-level exclusive scan over u32 items with a device-side length   */
-/*   XF 0: in = u32[];  XF 1: in = u64[], item = popcount;  XF 2: u32 != 0     */
-/*   n = (*n_ptr + add) >> shift                                              */
-/* ========================================================================== */
-static constexpr int SCAN_ITEMS = 8;                     /* per thread */
-static constexpr int SCAN_BLOCK = WG * SCAN_ITEMS;       /* 2048 per block */
-
-template <int XF>
-__device__ __forceinline__ uint32_t scan_item(const void *in, uint32_t i)
-{
-   if (XF == 0) return reinterpret_cast<const uint32_t *>(in)[i];
-   if (XF == 2) return reinterpret_cast<const uint32_t *>(in)[i] != 0u ? 1u : 0u;
-   return (uint32_t)__popcll(reinterpret_cast<const uint64_t *>(in)[i]);
-}
-
-template <int XF>
-__global__ __launch_bounds__(WG) void k_scan_reduce(const void *in, uint32_t *bsum, const uint32_t *n_ptr, uint32_t add,
-                                                    uint32_t shift)
-{
-   __shared__ uint32_t s_wave[4];
-   const uint32_t n = n_ptr ? (*n_ptr + add) >> shift : add;
-   const uint32_t base = blockIdx.x * SCAN_BLOCK;
-   if (base >= n) return;
-   uint32_t v = 0;
-#pragma unroll
-   for (int k = 0; k < SCAN_ITEMS; k++) {
-      const uint32_t i = base + threadIdx.x * SCAN_ITEMS + k;
-      if (i < n) v += scan_item<XF>(in, i);
-   }
-   uint32_t tot;
-   block_excl_scan(v, &tot, s_wave);
-   if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-/* One block: exclusive scan of bsum[0..nb) in place, total -> *total_out. */
-__global__ __launch_bounds__(WG) void k_scan_top(uint32_t *bsum, const uint32_t *n_ptr, uint32_t add, uint32_t shift,
-                                                 uint32_t *total_out)
-{
-   __shared__ uint32_t s_wave[4];
-   const uint32_t n = n_ptr ? (*n_ptr + add) >> shift : add;
-   const uint32_t nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-   uint32_t running = 0;
-   for (uint32_t b0 = 0; b0 < nb; b0 += WG) {
-      const uint32_t i = b0 + threadIdx.x;
-      const uint32_t v = i < nb ? bsum[i] : 0;
-      uint32_t tot;
-      const uint32_t ex = block_excl_scan(v, &tot, s_wave);
-      if (i < nb) bsum[i] = running + ex;
-      running += tot;
-   }
-   if (threadIdx.x == 0) *total_out = running;
-}
-
-template <int XF>
-__global__ __launch_bounds__(WG) void k_scan_apply(const void *in, uint32_t *out, const uint32_t *bsum,
-                                                   const uint32_t *n_ptr, uint32_t add, uint32_t shift)
-{
-   __shared__ uint32_t s_wave[4];
-   const uint32_t n = n_ptr ? (*n_ptr + add) >> shift : add;
-   const uint32_t base = blockIdx.x * SCAN_BLOCK;
-   if (base >= n) return;
-   uint32_t item[SCAN_ITEMS];
-   uint32_t v = 0;
-#pragma unroll
-   for (int k = 0; k < SCAN_ITEMS; k++) {
-      const uint32_t i = base + threadIdx.x * SCAN_ITEMS + k;
-      item[k] = i < n ? scan_item<XF>(in, i) : 0;
-      v += item[k];
-   }
-   uint32_t tot;
-   uint32_t ex = block_excl_scan(v, &tot, s_wave) + bsum[blockIdx.x];
-#pragma unroll
-   for (int k = 0; k < SCAN_ITEMS; k++) {
-      const uint32_t i = base + threadIdx.x * SCAN_ITEMS + k;
-      if (i < n) out[i] = ex;
-      ex += item[k];
-   }
-}
-
-/* ========================================================================== */
-/* K1: forward scan, one line per lane, 64 consecutive lines per wave          */
-/* ========================================================================== */
-template <int W>
-__device__ __forceinline__ void load_tables(const ScanArgs &a, uint32_t *s_peq, uint8_t *s_lut)
-{
-   for (int i = threadIdx.x; i < 10 * W; i += WG) {
-      /* a.peq holds [2][5][Wp] with Wp = words of the pattern; pad to W */
-      const int Wp = (a.m + 31) >> 5;
-      const int dir = i / (5 * W), rem = i % (5 * W), cls = rem / W, w = rem % W;
-      s_peq[i] = w < Wp ? a.peq[(dir * 5 + cls) * Wp + w] : 0u;
-   }
-   for (int b = threadIdx.x; b < 256; b += WG) s_lut[b] = sq_class_of((uint32_t)b, a.options);
-   __syncthreads();
-}
-
-template <int W>
-__global__ __launch_bounds__(WG) void k_forward(ScanArgs a)
-{
-   __shared__ uint32_t s_peq[10 * W];
-   __shared__ uint8_t s_lut[256];
-   load_tables<W>(a, s_peq, s_lut);
-   const uint32_t nlines = a.cnt->seg_nlines;
-   const int lane = threadIdx.x & 63;
-   const uint32_t wave = (blockIdx.x * WG + threadIdx.x) >> 6;
-   const uint32_t nwaves = (gridDim.x * WG) >> 6;
-   const bool fasta = (a.options & SEEQDEV_FASTA) != 0;
-   const uint32_t nchunks = (nlines + 63) >> 6;
-   for (uint32_t chunk = wave; chunk < nchunks; chunk += nwaves) {
-      const uint32_t idx = chunk * 64 + lane;
-      bool hit = false, hdr = false;
-      if (idx < nlines) {
-         const uint64_t off = a.seg_base + a.line_start[idx];
-         if (fasta && a.text[off] == '>') hdr = true;   /* off < nbytes: every line has >= 1 byte */
-         else
-            hit = sq_scan_line<W, SQ_MODE_ANY>(a.text, a.nbytes, off, (const uint32_t *)s_peq,
-                                               (const uint32_t *)(s_peq + 5 * W), (const uint8_t *)s_lut, a.m, a.tau,
-                                               a.options & 3, 0, nullptr, 0) != 0;
-      }
-      const uint64_t hm = __ballot(hit);
-      const uint64_t dm = __ballot(hdr);
-      if (lane == 0) {
-         a.hitmask[chunk] = hm;
-         if (fasta) a.hdrmask[chunk] = dm;
-      }
-   }
-}
-
-__device__ __forceinline__ uint32_t counted_line_no(const ScanArgs &a, uint32_t idx, bool fasta)
-{
-   /* 1-based index among counted lines of the whole buffer (reference seeq.c:377) */
-   uint64_t n = a.cnt->lines + idx + 1;
-   if (fasta) {
-      const uint32_t chunk = idx >> 6;
-      n -= a.hdr_off[chunk] + (uint32_t)__popcll(a.hdrmask[chunk] & ((1ull << (idx & 63)) - 1));
-   }
-   return (uint32_t)n;
-}
-
-/* ========================================================================== */
-/* K3: ordered compaction of hit lines                                        */
-/* ========================================================================== */
-__global__ __launch_bounds__(WG) void k_compact(ScanArgs a)
-{
-   const uint32_t nlines = a.cnt->seg_nlines;
-   const uint32_t nchunks = (nlines + 63) >> 6;
-   const int lane = threadIdx.x & 63;
-   const uint32_t wave = (blockIdx.x * WG + threadIdx.x) >> 6;
-   const uint32_t nwaves = (gridDim.x * WG) >> 6;
-   const bool fasta = (a.options & SEEQDEV_FASTA) != 0;
-   for (uint32_t chunk = wave; chunk < nchunks; chunk += nwaves) {
-      const uint64_t hm = a.hitmask[chunk];
-      if ((hm >> lane) & 1) {
-         const uint32_t k = a.wave_off[chunk] + (uint32_t)__popcll(hm & ((1ull << lane) - 1));
-         if (k < a.cap_hitlines) {
-            const uint32_t idx = chunk * 64 + lane;
-            a.hit_start[k] = a.line_start[idx];
-            a.hit_line[k] = counted_line_no(a, idx, fasta);
-         }
-      }
-   }
-}
-
-/* After compaction: overflow check of the hit-line list; for FIRST/BEST the
- * number of records of the segment is the number of hit lines. */
-__global__ void k_seg_mid(ScanArgs a)
-{
-   Counters *c = a.cnt;
-   uint32_t nhl = c->seg_nhitlines;
-   if (nhl > c->need_hitlines) c->need_hitlines = nhl;
-   if (nhl > a.cap_hitlines) {
-      atomicOr(&c->overflow, OVF_HITLINES);
-      nhl = 0;
-      c->seg_nhitlines = 0;      /* totals of this run are void anyway */
-   }
-   c->seg_nrec = nhl;            /* overwritten by the nh scan for SQ_ALL / COUNTMATCH */
-}
-
-__global__ void k_rec_check(ScanArgs a) { rec_check_body(a); }
-
-/* ========================================================================== */
-/* K4/K5: exact pass over the hit lines                                       */
-/* ========================================================================== */
-template <int W, int MODE>
-__global__ __launch_bounds__(WG) void k_exact(ScanArgs a)
-{
-   __shared__ uint32_t s_peq[10 * W];
-   __shared__ uint8_t s_lut[256];
-   load_tables<W>(a, s_peq, s_lut);
-   const Counters *c = a.cnt;
-   const uint32_t nhl = c->seg_nhitlines;
-   const int match_opt = a.options & 3;
-   if (MODE == SQ_MODE_EMIT && (c->overflow & OVF_RECORDS)) return;
-   const uint32_t stride = gridDim.x * WG;
-   for (uint32_t k = blockIdx.x * WG + threadIdx.x; k < nhl; k += stride) {
-      const uint64_t off = a.seg_base + a.hit_start[k];
-      if (MODE == SQ_MODE_COUNT) {
-         a.nh[k] = sq_scan_line<W, SQ_MODE_COUNT>(a.text, a.nbytes, off, (const uint32_t *)s_peq,
-                                                  (const uint32_t *)(s_peq + 5 * W), (const uint8_t *)s_lut, a.m,
-                                                  a.tau, match_opt, 0, nullptr, 0);
-      } else {
-         const uint32_t line_no = a.hit_line[k];
-         uint64_t dst;
-         uint32_t cap;
-         if (match_opt == SQ_ALL) {
-            dst = c->records + a.nh[k];
-            cap = 0xFFFFFFFFu;       /* exact count known from the COUNT pass */
-         } else {
-            dst = c->records + (a.use_nh ? a.nh[k] : k);
-            cap = 1;
-         }
-         sq_scan_line<W, SQ_MODE_EMIT>(a.text, a.nbytes, off, (const uint32_t *)s_peq,
-                                       (const uint32_t *)(s_peq + 5 * W), (const uint8_t *)s_lut, a.m, a.tau,
-                                       match_opt, line_no, reinterpret_cast<sq_hit_t *>(a.records + dst), cap);
-      }
-   }
-}
-
-/* Per record: where its line starts in the buffer (lets the host jump from hit to hit instead of
-   walking every line: the replay of seeqFileMatch, seeq.c:361-386, becomes O(hits)). */
-__global__ __launch_bounds__(WG) void k_rec_offsets(ScanArgs a)
-{
-   const Counters *c = a.cnt;
-   if (c->overflow & OVF_RECORDS) return;
-   const uint32_t nhl = c->seg_nhitlines;
-   const bool all = (a.options & 3) == SQ_ALL || a.use_nh;
-   const uint32_t stride = gridDim.x * WG;
-   for (uint32_t k = blockIdx.x * WG + threadIdx.x; k < nhl; k += stride) {
-      const uint64_t off = a.seg_base + a.hit_start[k];
-      if (all) {
-         const uint32_t lo = a.nh[k], hi = k + 1 < nhl ? a.nh[k + 1] : c->seg_nrec;
-         for (uint32_t r = lo; r < hi; r++) a.rec_off[c->records + r] = off;
-      } else {
-         a.rec_off[c->records + k] = off;
-      }
-   }
-}
-
-/* Lines with >= 1 verified hit, from the per-line counts (before they are scanned into offsets). */
-__device__ __forceinline__ void count_nonzero_body(const ScanArgs &a)
-{
-   __shared__ uint32_t s_n[WG / 64];
-   const uint32_t nhl = a.cnt->seg_nhitlines;
-   const uint32_t stride = gridDim.x * WG;
-   uint32_t n = 0;
-   for (uint32_t k = blockIdx.x * WG + threadIdx.x; k < nhl; k += stride) n += a.nh[k] != 0;
-#pragma unroll
-   for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
-   if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = n;
-   __syncthreads();
-   if (threadIdx.x == 0) {                                 /* one atomic per block: same-address atomics serialise */
-      n = 0;
-      for (int w = 0; w < WG / 64; w++) n += s_n[w];
-      if (n) atomicAdd(&a.cnt->seg_nmatch, n);
-   }
-}
-__global__ __launch_bounds__(WG) void k_count_nonzero(ScanArgs a) { count_nonzero_body(a); }
-
-__global__ void k_seg_end(ScanArgs a, int flags) { seg_end_body(a, flags); }
-
-/* SINGLELINE: the buffer is one string -> one line starting at 0. */
-__global__ void k_single_line(ScanArgs a)
-{
-   a.cnt->seg_nlines = 1;
-   if (a.cnt->need_lines < 1) a.cnt->need_lines = 1;
-   a.line_start[0] = 0;
-}
-
+#include "seeq_generic.h"
+#include "seeq_scan.h"
 #include "seeq_fused_post.h"
 #include "seeq_direct.h"
 #include "seeq_exact1.h"
@@ -455,78 +112,7 @@ static_assert(STREAM_NW == STREAM_NW_HOST, "waves per k_stream workgroup");
 extern "C" {
 #include "seeq_dfa.h"
 }
-
-/* ========================================================================== */
-/* Synthetic reads (bench / test input; CPU twin: oracle/seeq_oracle.c)        */
-/* ========================================================================== */
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
-{
-   x += 0x9E3779B97F4A7C15ull;
-   uint64_t z = x;
-   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-   return z ^ (z >> 31);
-}
-
-struct SynthArgs {
-   uint8_t *out;
-   uint64_t first, n, seed;
-   int len, plen, tau;
-   char pattern[96];
-};
-
-__global__ __launch_bounds__(WG) void k_synth(SynthArgs s)
-{
-   const uint64_t k = (uint64_t)blockIdx.x * WG + threadIdx.x;
-   if (k >= s.n) return;
-   const uint64_t r = s.first + k;
-   uint8_t *line = s.out + k * (uint64_t)(s.len + 1);
-   const char B[4] = {'A', 'C', 'G', 'T'};
-   for (int p = 0; p < s.len; p++) line[p] = B[splitmix64(s.seed ^ (r * 256 + (uint64_t)p)) >> 62];
-   line[s.len] = '\n';
-   const uint64_t hr = splitmix64(s.seed ^ 0xA5A5A5A5DEADBEEFull ^ (r * 0x100000001B3ull));
-   if ((hr & 15) == 0 && s.plen > 0 && s.plen + s.tau + 2 <= 96 && s.plen + s.tau + 2 <= s.len) {
-      char t[96];
-      int cur = s.plen;
-      for (int i = 0; i < s.plen; i++) t[i] = s.pattern[i];
-      const int e = (int)((hr >> 4) % (uint64_t)(s.tau + 3));
-      for (int q = 0; q < e; q++) {
-         const uint64_t hk = splitmix64(hr + (uint64_t)q + 1);
-         const int type = (int)(hk % 3);
-         const int pos = (int)((hk >> 8) % (uint64_t)cur);
-         const char b = B[(hk >> 40) & 3];
-         if (type == 0) t[pos] = b;
-         else if (type == 1) {
-            for (int u = cur; u > pos; u--) t[u] = t[u - 1];
-            t[pos] = b;
-            cur++;
-         } else if (cur > 1) {
-            for (int u = pos; u < cur - 1; u++) t[u] = t[u + 1];
-            cur--;
-         }
-      }
-      const int off = (int)((hr >> 20) % (uint64_t)(s.len - cur + 1));
-      for (int i = 0; i < cur; i++) line[off + i] = (uint8_t)t[i];
-   }
-   const uint64_t hn = splitmix64(s.seed ^ 0x5BD1E9955BD1E995ull ^ (r * 0x9E3779B1ull));
-   if ((hn & 255) == 0) line[(hn >> 8) % (uint64_t)s.len] = 'N';
-}
-
-extern "C" int seeqdevSynthReads(void *d_out, uint64_t first, uint64_t n, int len, const char *pattern_plain, int plen,
-                                 int tau, uint64_t seed, void *hip_stream)
-{
-   if (!d_out || len <= 0 || plen < 0 || plen > 96) { seeqerr = 0; errno = EINVAL; return -1; }
-   if (n == 0) return 0;
-   SynthArgs s;
-   memset(&s, 0, sizeof s);
-   s.out = (uint8_t *)d_out; s.first = first; s.n = n; s.seed = seed; s.len = len; s.plen = plen; s.tau = tau;
-   memcpy(s.pattern, pattern_plain, (size_t)plen);
-   const uint64_t blocks = (n + WG - 1) / WG;
-   if (blocks > 0x7FFFFFFFull) { seeqerr = 0; errno = E2BIG; return -1; }
-   hipLaunchKernelGGL(k_synth, dim3((unsigned)blocks), dim3(WG), 0, (hipStream_t)hip_stream, s);
-   HIP_TRY(hipGetLastError(), EIO);
-   return 0;
-}
+#include "seeq_synth.h"
 
 /* ========================================================================== */
 /* Pattern handle                                                             */
@@ -562,6 +148,10 @@ struct seeqdev_pattern {
    double    quad_pacc;
    pthread_mutex_t plan_lock;   /* the automata are built on first use; scan contexts on several threads may share a pattern */
 };
+
+/* FN<W>(...) for the W that holds a pattern of `words` Peq words: the five instances of the kernels templated on it (k_forward, k_exact, k_string) */
+#define SEEQ_FOR_WORDS(words, FN, ...) \
+   ((words) <= 1 ? FN<1>(__VA_ARGS__) : (words) <= 2 ? FN<2>(__VA_ARGS__) : (words) <= 4 ? FN<4>(__VA_ARGS__) : (words) <= 8 ? FN<8>(__VA_ARGS__) : FN<16>(__VA_ARGS__))
 
 extern "C" seeqdev_pattern_t *seeqdevPatternNew(const char *keys, int wlen, int tau)
 {
@@ -944,6 +534,17 @@ static void ws_hip_release(void *, int kind, void *p)
    else (void)hipHostFree(p);
 }
 
+/* ws_grow_keep: work on the context's stream may still write the old block -- wait for it, then device to device (and wait), or memcpy */
+static int ws_hip_copy(void *ctx, int kind, void *dst, const void *src, size_t bytes)
+{
+   const hipStream_t st = ((seeqdev_scan *)ctx)->stream;
+   HIP_TRY(hipStreamSynchronize(st), EIO);
+   if (kind != WS_DEVICE) { memcpy(dst, src, bytes); return 0; }
+   HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st), EIO);
+   HIP_TRY(hipStreamSynchronize(st), EIO);
+   return 0;
+}
+
 extern "C" seeqdev_scan_t *seeqdevScanNew(void *hip_stream)
 {
    seeqerr = 0;
@@ -955,9 +556,7 @@ extern "C" seeqdev_scan_t *seeqdevScanNew(void *hip_stream)
    seeqdev_scan *s = (seeqdev_scan *)calloc(1, sizeof *s);
    if (!s) return NULL;
    if (hipGetDevice(&s->device) != hipSuccess) s->device = 0;
-   s->ws.hooks = {ws_hip_alloc, ws_hip_release, NULL};
-   /* (these three carry their contents over when they grow -- demux_ws_out, multi_grow_host, seeqdevStringMatch --: grown there, freed with the rest) */
-   ws_adopt(&s->ws, s->dm_out, WS_DEVICE); ws_adopt(&s->ws, s->multi_rec, WS_PINNED); ws_adopt(&s->ws, s->h_strout, WS_COHERENT);
+   s->ws.hooks = {ws_hip_alloc, ws_hip_release, s, ws_hip_copy};
    s->seg_bytes = (size_t)0xF0000000u;      /* 3.75 GiB segments: u32 offsets with room for k_stream's bias; multiple of every tile size */
    const char *env = getenv("SEEQ_SEGMENT_BYTES");
    if (env && atoll(env) >= 65536) s->seg_bytes = ((size_t)atoll(env) + 15) & ~(size_t)15;
@@ -1113,118 +712,6 @@ extern "C" int seeqdevScanLastTimes(const seeqdev_scan_t *s, float ms[4])
    if (!s || !ms) { errno = EINVAL; return -1; }
    for (int i = 0; i < 4; i++) ms[i] = s->acc_ms[i];
    return 0;
-}
-
-/* Up to three u32 arrays of the same host-known length scanned in place by ONE set of three launches (the per-tile
- * arrays of the one-pass kernels): blockIdx.y selects the array, bsum has one region of `nb` partial sums per array. */
-struct ScanSet { uint32_t *arr[3]; uint32_t *total[3]; };
-
-__global__ __launch_bounds__(WG) void k_scanset_reduce(ScanSet ss, uint32_t *bsum, uint32_t n, uint32_t nb)
-{
-   __shared__ uint32_t s_wave[4];
-   const uint32_t *in = ss.arr[blockIdx.y];
-   const uint32_t base = blockIdx.x * SCAN_BLOCK;
-   uint32_t v = 0;
-#pragma unroll
-   for (int k = 0; k < SCAN_ITEMS; k++) {
-      const uint32_t i = base + threadIdx.x * SCAN_ITEMS + k;
-      if (i < n) v += in[i];
-   }
-   uint32_t tot;
-   block_excl_scan(v, &tot, s_wave);
-   if (threadIdx.x == 0) bsum[blockIdx.y * nb + blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(WG) void k_scanset_top(ScanSet ss, uint32_t *bsum, uint32_t nb)
-{
-   __shared__ uint32_t s_wave[4];
-   uint32_t *b = bsum + blockIdx.x * nb;
-   uint32_t running = 0;
-   for (uint32_t b0 = 0; b0 < nb; b0 += WG) {
-      const uint32_t i = b0 + threadIdx.x;
-      const uint32_t v = i < nb ? b[i] : 0;
-      uint32_t tot;
-      const uint32_t ex = block_excl_scan(v, &tot, s_wave);
-      if (i < nb) b[i] = running + ex;
-      running += tot;
-      __syncthreads();
-   }
-   if (threadIdx.x == 0 && ss.total[blockIdx.x]) *ss.total[blockIdx.x] = running;
-}
-
-__global__ __launch_bounds__(WG) void k_scanset_apply(ScanSet ss, const uint32_t *bsum, uint32_t n, uint32_t nb)
-{
-   __shared__ uint32_t s_wave[4];
-   uint32_t *arr = ss.arr[blockIdx.y];
-   const uint32_t base = blockIdx.x * SCAN_BLOCK;
-   uint32_t item[SCAN_ITEMS];
-   uint32_t v = 0;
-#pragma unroll
-   for (int k = 0; k < SCAN_ITEMS; k++) {
-      const uint32_t i = base + threadIdx.x * SCAN_ITEMS + k;
-      item[k] = i < n ? arr[i] : 0;
-      v += item[k];
-   }
-   uint32_t tot;
-   uint32_t ex = block_excl_scan(v, &tot, s_wave) + bsum[blockIdx.y * nb + blockIdx.x];
-#pragma unroll
-   for (int k = 0; k < SCAN_ITEMS; k++) {
-      const uint32_t i = base + threadIdx.x * SCAN_ITEMS + k;
-      if (i < n) arr[i] = ex;
-      ex += item[k];
-   }
-}
-
-/* ---- launch helpers ------------------------------------------------------- */
-template <int XF>
-static void launch_scan(seeqdev_scan *s, hipStream_t st, const void *in, uint32_t *out, size_t cap_items, const uint32_t *n_ptr,
-                        uint32_t add, uint32_t shift, uint32_t *total_out)
-{
-   const unsigned nb = (unsigned)((cap_items + SCAN_BLOCK - 1) / SCAN_BLOCK);
-   if (nb == 0) return;
-   hipLaunchKernelGGL(k_scan_reduce<XF>, dim3(nb), dim3(WG), 0, st, in, s->scan_ws, n_ptr, add, shift);
-   hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(WG), 0, st, s->scan_ws, n_ptr, add, shift, total_out);
-   hipLaunchKernelGGL(k_scan_apply<XF>, dim3(nb), dim3(WG), 0, st, in, out, (const uint32_t *)s->scan_ws,
-                      n_ptr, add, shift);
-}
-
-static void launch_scanset(seeqdev_scan *s, hipStream_t st, uint32_t *a0, uint32_t *a1, uint32_t *a2, uint32_t n, uint32_t *t0, uint32_t *t1, uint32_t *t2)
-{
-   const unsigned nb = (unsigned)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
-   if (nb == 0) return;
-   ScanSet ss = {{a0, a1, a2}, {t0, t1, t2}};
-   const unsigned na = a2 ? 3 : a1 ? 2 : 1;
-   hipLaunchKernelGGL(k_scanset_reduce, dim3(nb, na), dim3(WG), 0, st, ss, s->scan_ws, n, nb);
-   hipLaunchKernelGGL(k_scanset_top, dim3(na), dim3(WG), 0, st, ss, s->scan_ws, nb);
-   hipLaunchKernelGGL(k_scanset_apply, dim3(nb, na), dim3(WG), 0, st, ss, (const uint32_t *)s->scan_ws, n, nb);
-}
-
-/* The tile_cnt scan has a host-known length (ntiles); a dedicated small kernel
- * avoids routing a host constant through device memory. */
-__global__ __launch_bounds__(WG) void k_scan_tiles(uint32_t *tile_cnt, uint32_t ntiles, uint32_t *total_out)
-{
-   __shared__ uint32_t s_wave[4];
-   uint32_t running = 0;
-   for (uint32_t b0 = 0; b0 < ntiles; b0 += WG * SCAN_ITEMS) {
-      uint32_t item[SCAN_ITEMS];
-      uint32_t v = 0;
-#pragma unroll
-      for (int k = 0; k < SCAN_ITEMS; k++) {
-         const uint32_t i = b0 + threadIdx.x * SCAN_ITEMS + k;
-         item[k] = i < ntiles ? tile_cnt[i] : 0;
-         v += item[k];
-      }
-      uint32_t tot;
-      uint32_t ex = running + block_excl_scan(v, &tot, s_wave);
-#pragma unroll
-      for (int k = 0; k < SCAN_ITEMS; k++) {
-         const uint32_t i = b0 + threadIdx.x * SCAN_ITEMS + k;
-         if (i < ntiles) tile_cnt[i] = ex;
-         ex += item[k];
-      }
-      running += tot;
-   }
-   if (threadIdx.x == 0) *total_out = running;
 }
 
 /* Workgroups of `fn` (threads per workgroup, dynamic LDS) that fit one CU; asked once per kernel and LDS size.
@@ -1513,7 +1000,7 @@ static int seg_onepass(seeqdev_scan *s, const SegRun &r, ScanArgs &a, size_t sg,
    }
    else hipLaunchKernelGGL(k_fused_post, dim3(1), dim3(256), 0, st, f, (uint32_t)nsl);
    if (!order2 && (s->want != SEEQDEV_WANT_COUNTLINES || plan.superset)) {
-      launch_scanset(s, st, f.tile_hits, f.tile_cl, f.tile_dirty, f.ntiles, nullptr, nullptr, f.tile_dirty ? &s->d_cnt->seg_dirty_tiles : nullptr);
+      launch_scanset(st, s->scan_ws, f.tile_hits, f.tile_cl, f.tile_dirty, f.ntiles, nullptr, nullptr, f.tile_dirty ? &s->d_cnt->seg_dirty_tiles : nullptr);
       if (plan.use_stream) hipLaunchKernelGGL(k_stream_reorder, dim3(rgrid), dim3(256), 0, st, f, (uint32_t)nsl, s->hit_start, s->hit_line, s->nh, s->hit_col);
       else hipLaunchKernelGGL(k_fused_reorder, dim3(rgrid), dim3(256), 0, st, f, (uint32_t)nsl, s->hit_start, s->hit_line);
    }
@@ -1548,8 +1035,8 @@ static int seg_index_forward(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipE
    hipLaunchKernelGGL(k_forward<W>, dim3(r.grid_lines), dim3(WG), 0, st, a);
    if (ev) HIP_TRY(hipEventRecord(ev[2], st), EIO);
    /* ---- K2: ranks of hit lines (and FASTA headers) ---- */
-   launch_scan<1>(s, st, a.hitmask, a.wave_off, s->cap_chunks, &c->seg_nlines, 63u, 6u, &c->seg_nhitlines);
-   if (s->options & SEEQDEV_FASTA) launch_scan<1>(s, st, a.hdrmask, a.hdr_off, s->cap_chunks, &c->seg_nlines, 63u, 6u, &c->seg_nheaders);
+   launch_scan<1>(st, s->scan_ws, a.hitmask, a.wave_off, s->cap_chunks, &c->seg_nlines, 63u, 6u, &c->seg_nhitlines);
+   if (s->options & SEEQDEV_FASTA) launch_scan<1>(st, s->scan_ws, a.hdrmask, a.hdr_off, s->cap_chunks, &c->seg_nlines, 63u, 6u, &c->seg_nheaders);
    return 0;
 }
 
@@ -1636,7 +1123,7 @@ static int seg_post(seeqdev_scan *s, const SegRun &r, ScanArgs &a, hipEvent_t *e
          else hipLaunchKernelGGL(k_lead_lines, dim3(grid_hits < 512 ? grid_hits : 512), dim3(256), 0, st, a, (const uint32_t *)s->lead_fidx, s->lead_flag);
       }
       else if (plan.superset && plan.nh_is_count) hipLaunchKernelGGL(k_count_nonzero, dim3(grid_hits < 512 ? grid_hits : 512), dim3(WG), 0, st, a);
-      launch_scan<0>(s, st, a.nh, a.nh, s->cap_hitlines, &c->seg_nhitlines, 0u, 0u, &c->seg_nrec);
+      launch_scan<0>(st, s->scan_ws, a.nh, a.nh, s->cap_hitlines, &c->seg_nhitlines, 0u, 0u, &c->seg_nrec);
    }
    /* ---- K5: records ---- */
    if (want == SEEQDEV_WANT_RECORDS && !emitted) {
@@ -1794,7 +1281,7 @@ static int run_packed(seeqdev_scan *s)
       }
       if (ev) HIP_TRY(hipEventRecord(ev[2], st), EIO);
       /* candidates before every block of 64 reads, their number */
-      launch_scanset(s, st, s->pk_coff, nullptr, nullptr, (p.nreads + 63u) >> 6, &c->seg_nhitlines, nullptr, nullptr);
+      launch_scanset(st, s->scan_ws, s->pk_coff, nullptr, nullptr, (p.nreads + 63u) >> 6, &c->seg_nhitlines, nullptr, nullptr);
       hipLaunchKernelGGL(k_packed_counts, dim3(1), dim3(1), 0, st, p);
       hipLaunchKernelGGL(k_packed_list, dim3((unsigned)(((size_t)p.nreads / 1024 + 4) / 4)), dim3(256), 0, st, p);      /* a wave per 16 blocks of 64 reads */
       /* from here: the exact pass over the staging text, as behind k_pair */
@@ -1840,151 +1327,26 @@ static int run_packed(seeqdev_scan *s)
    return 0;
 }
 
-/* ========================================================================== */
-/* Several patterns, one walk (seeq_multi.h)                                    */
-/* ========================================================================== */
-static int multi_ws_ensure(seeqdev_scan *s, int npat)
-{
-   Workspace *w = &s->ws;
-   const size_t hl = s->cap_hitlines;
-   if (ws_make(w, {{s->d_mcnt, SEEQ_MULTI_MAX * sizeof(Counters)}, {s->h_mcnt, SEEQ_MULTI_MAX * sizeof(Counters), WS_PINNED}})) return -1;
-   if (ws_grow(w, &s->cap_ml, hl, {{s->ml_mask, hl * sizeof(uint32_t)}, {s->ml_first, hl * sizeof(uint32_t)}, {s->ml_last, hl * sizeof(uint32_t)}})) return -1;
-   if (ws_grow(w, &s->cap_mp, hl, {{s->mp_idx, hl * sizeof(uint32_t)}, {s->mp_nh, hl * sizeof(uint32_t)}})) return -1;
-   if (!s->d_mx) {
-      const size_t slots = 64;                             /* segments whose argument arrays may be in flight (a run of more segments waits for the stream in between) */
-      if (ws_make(w, {{s->d_mx, slots * SEEQ_MULTI_MAX * sizeof(MultiExact)}, {s->h_mx, slots * SEEQ_MULTI_MAX * sizeof(MultiExact), WS_PINNED}})) return -1;
-      s->mx_slots = slots;
-      s->mx_next = 0;
-   }
-   const size_t nbp = (hl / (size_t)npat) / SCAN_BLOCK + 2, nb = hl / MULTI_BLOCK + 2;
-   if (ws_grow(w, &s->cap_m_scan_ws, (size_t)npat * nbp, {{s->m_scan_ws, (size_t)npat * nbp * sizeof(uint32_t)}})) return -1;
-   return ws_grow(w, &s->cap_m_bsum, (size_t)npat * nb, {{s->m_bsum, (size_t)npat * nb * sizeof(uint32_t)}});
-}
-
-/* The part of a segment behind the union walk: `ua` = the union scan's arguments (hit list made, bounds done). */
-static int multi_post(seeqdev_scan *s, const ScanPlan &plan, const ScanArgs &ua, hipStream_t st)
-{
-   const MultiPlan *mp = s->mplan;
-   const int npat = mp->npat;
-   const int options = s->options, want = s->want;
-   const int match_opt = options & 3;
-   const uint32_t capP = (uint32_t)(s->cap_hitlines / (size_t)npat);
-   const uint64_t capR = s->cap_records / (uint64_t)npat;
-   MultiArgs m;
-   memset(&m, 0, sizeof m);
-   m.text = ua.text; m.nbytes = ua.nbytes; m.seg_base = ua.seg_base;
-   m.hit_start = s->hit_start; m.hit_line = s->hit_line; m.hit_col = s->hit_col; m.nh = s->nh;
-   m.ucnt = s->d_cnt;
-   m.res_next = mp->d_res_next; m.res_mask = mp->d_res_mask; m.res_states = mp->res_states;
-   m.maxspan = (uint32_t)mp->maxspan;
-   m.window_ok = ua.window_ok;
-   m.options = options;
-   /* whole patterns in the resolve automaton: its sets are exact -- counting lines needs no exact pass (as behind k_stream's complete automata) */
-   const bool trust = mp->exact && want == SEEQDEV_WANT_COUNTLINES;
-   m.trust = trust ? 1u : 0u;
-   m.lmask = s->ml_mask; m.lfirst = s->ml_first; m.llast = s->ml_last;
-   m.npat = (uint32_t)npat; m.capP = capP;
-   m.p_idx = s->mp_idx;
-   m.pcnt = s->d_mcnt;
-   m.bsum = s->m_bsum;
-   m.nb = (uint32_t)(s->cap_hitlines / MULTI_BLOCK + 2);
-   {
-      const size_t blocks = (s->cap_hitlines + MULTI_RESOLVE_WG - 1) / MULTI_RESOLVE_WG;
-      const unsigned grid = (unsigned)(blocks < (size_t)s->ncu * 2 ? blocks : (size_t)s->ncu * 2);      /* persistent: the table is staged once per workgroup */
-      HIP_TRY(hipMemsetAsync(s->ml_mask, 0, s->cap_hitlines * sizeof(uint32_t), st), EIO);      /* the lanes of a line's entries OR / MAX into them */
-      HIP_TRY(hipMemsetAsync(s->ml_last, 0, s->cap_hitlines * sizeof(uint32_t), st), EIO);
-      /* the automaton in LDS when it fits what a workgroup may ask for beside the kernel's static arrays (the device's limit, not a literal) */
-      const size_t lds2 = (size_t)mp->res_states * 20, lds1 = (size_t)mp->res_states * 16;
-      const size_t lds_room = s->lds_per_wg > 1024 ? s->lds_per_wg - 1024 : 0;
-      HIP_TRY(hipGetLastError(), EIO);                       /* (an error of an EARLIER launch of this segment is a failure, not a reason for the per-pattern fall-back) */
-      if (lds2 <= lds_room && lds2 <= 65536) hipLaunchKernelGGL(k_multi_resolve<2>, dim3(grid ? grid : 1), dim3(MULTI_RESOLVE_WG), lds2, st, m);
-      else if (lds1 <= lds_room && lds1 <= 65536) hipLaunchKernelGGL(k_multi_resolve<1>, dim3(grid ? grid : 1), dim3(MULTI_RESOLVE_WG), lds1, st, m);
-      else hipLaunchKernelGGL(k_multi_resolve<0>, dim3(grid ? grid : 1), dim3(MULTI_RESOLVE_WG), 0, st, m);
-      {
-         const hipError_t le = hipGetLastError();            /* this launch refused for its resources: a scan per pattern (seeqdevScanRunMulti); anything else fails */
-         if (le == hipErrorInvalidValue || le == hipErrorLaunchOutOfResources || le == hipErrorInvalidConfiguration) return 1;
-         if (le != hipSuccess) return hip_fail(le, "k_multi_resolve", EIO);
-      }
-      hipLaunchKernelGGL(k_multi_reduce, dim3(m.nb), dim3(256), 0, st, m);
-      hipLaunchKernelGGL(k_multi_top, dim3((unsigned)npat), dim3(256), 0, st, m);
-      if (trust) { HIP_TRY(hipGetLastError(), EIO); return 0; }
-      hipLaunchKernelGGL(k_multi_apply, dim3(m.nb), dim3(256), 0, st, m);
-   }
-   /* The exact pass, every pattern in one launch per step (blockIdx.y = pattern; one-word patterns first, then the two-word
-      ones): the patterns' arguments go to HBM through a page-locked ring, one slot per segment. */
-   const unsigned grid_hits = capped_grid(s, capP, 4);      /* (x npat workgroups per launch) */
-   if (s->mx_next == s->mx_slots) { HIP_TRY(hipStreamSynchronize(st), EIO); s->mx_next = 0; }
-   MultiExact *hx = s->h_mx + s->mx_next * SEEQ_MULTI_MAX, *dx = s->d_mx + s->mx_next * SEEQ_MULTI_MAX;
-   s->mx_next++;
-   const uint32_t nbp = (uint32_t)((size_t)capP / SCAN_BLOCK + 2);
-   int order[SEEQ_MULTI_MAX], n1 = 0, n2 = 0;
-   for (int k = 0; k < npat; k++) if (mp->fw[k] == 1) order[n1++] = k;
-   for (int k = 0; k < npat; k++) if (mp->fw[k] != 1) order[n1 + n2++] = k;
-   for (int q = 0; q < npat; q++) {
-      const int k = order[q];
-      MultiExact &x = hx[q];
-      ScanArgs &a = x.a;
-      a = ua;
-      a.m = mp->m[k]; a.tau = mp->tau[k];
-      a.hit_start = s->hit_start; a.hit_line = s->hit_line; a.cap_hitlines = capP;      /* the union's lines, through this pattern's index list */
-      a.hit_idx = s->mp_idx + (size_t)k * capP;
-      a.nh = s->mp_nh + (size_t)k * capP;
-      a.records = s->records + (uint64_t)k * capR; a.cap_records = capR; a.rec_off = s->rec_off + (uint64_t)k * capR;
-      a.use_nh = 3u; a.filter = 1u;
-      a.skip_back = (uint32_t)mp->maxspan;
-      a.hit_last = s->ml_last;
-      a.window_ok = 1u;
-      a.tile_dirty = nullptr; a.tile_dmask = nullptr; a.stream_ntiles = 0; a.stream_ch = 0;
-      a.cnt = s->d_mcnt + k;
-      x.eq = mp->d_eq + (size_t)k * 1536;
-      x.hcol = s->ml_first;
-      x.cache = want == SEEQDEV_WANT_RECORDS ? s->ow.tmp + (size_t)k * capP : nullptr;
-      x.scan_ws = s->m_scan_ws + (size_t)k * nbp;
-      x.nb = nbp;
-      x.seg_end_flags = seg_end_flags(plan.need_nh, plan.superset, plan.nh_is_count);
-   }
-   HIP_TRY(hipMemcpyAsync(dx, hx, (size_t)npat * sizeof(MultiExact), hipMemcpyHostToDevice, st), EIO);
-   const int mo = match_opt == SQ_COUNT ? SQ_FIRST : match_opt;
-   if (n1) hipLaunchKernelGGL((k_exact1m<SQ_MODE_COUNT, 1, -1>), dim3(grid_hits, (unsigned)n1), dim3(WG), 0, st, (const MultiExact *)dx);
-   if (n2) hipLaunchKernelGGL((k_exact1m<SQ_MODE_COUNT, 2, -1>), dim3(grid_hits, (unsigned)n2), dim3(WG), 0, st, (const MultiExact *)(dx + n1));
-   if (plan.nh_is_count) hipLaunchKernelGGL(k_multi_count_nonzero, dim3(grid_hits < 128 ? grid_hits : 128, (unsigned)npat), dim3(WG), 0, st, (const MultiExact *)dx);
-   hipLaunchKernelGGL(k_multi_scan_reduce, dim3(nbp, (unsigned)npat), dim3(WG), 0, st, (const MultiExact *)dx);
-   hipLaunchKernelGGL(k_multi_scan_top, dim3((unsigned)npat), dim3(WG), 0, st, (const MultiExact *)dx, want == SEEQDEV_WANT_RECORDS ? 1 : 0);
-   hipLaunchKernelGGL(k_multi_scan_apply, dim3(nbp, (unsigned)npat), dim3(WG), 0, st, (const MultiExact *)dx);
-   if (want == SEEQDEV_WANT_RECORDS) {
-      if (mo == SQ_BEST) {
-         if (n1) hipLaunchKernelGGL((k_exact1m<SQ_MODE_EMIT, 1, SQ_BEST>), dim3(grid_hits, (unsigned)n1), dim3(WG), 0, st, (const MultiExact *)dx);
-         if (n2) hipLaunchKernelGGL((k_exact1m<SQ_MODE_EMIT, 2, SQ_BEST>), dim3(grid_hits, (unsigned)n2), dim3(WG), 0, st, (const MultiExact *)(dx + n1));
-      } else {
-         if (n1) hipLaunchKernelGGL((k_exact1m<SQ_MODE_EMIT, 1, -1>), dim3(grid_hits, (unsigned)n1), dim3(WG), 0, st, (const MultiExact *)dx);
-         if (n2) hipLaunchKernelGGL((k_exact1m<SQ_MODE_EMIT, 2, -1>), dim3(grid_hits, (unsigned)n2), dim3(WG), 0, st, (const MultiExact *)(dx + n1));
-      }
-   }
-   hipLaunchKernelGGL(k_multi_seg_end, dim3((unsigned)npat), dim3(1), 0, st, (const MultiExact *)dx);
-   HIP_TRY(hipGetLastError(), EIO);
-   return 0;
-}
 
 static int dispatch_run(seeqdev_scan *s)
 {
    if (s->is_packed) return run_packed(s);
-   const int W = s->pat->words;
-   if (W <= 1) return run_segments<1>(s);
-   if (W <= 2) return run_segments<2>(s);
-   if (W <= 4) return run_segments<4>(s);
-   if (W <= 8) return run_segments<8>(s);
-   return run_segments<16>(s);
+   return SEEQ_FOR_WORDS(s->pat->words, run_segments, s);
 }
 
-static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const void *d_text, size_t nbytes, int options, int want, int hl_div);
-
-extern "C" int seeqdevScanRun(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const void *d_text, size_t nbytes,
-                              int options, int want)
+/* The argument rules the scan entries share: a context, `want` in range, every pattern there and on the context's device, SEEQDEV_FASTQ not
+   beside FASTA / SINGLELINE / input-mask bits.  0: one is broken (the entry's EINVAL; a foreign device is named in the error text). */
+static int scan_args_ok(const seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, int options, int want)
 {
-   if (scan_setup(s, pat, d_text, nbytes, options, want, SEEQ_HL_DIV)) return -1;
-   if (dispatch_run(s)) return -1;
-   s->ran = true;
-   return 0;
+   if (!s || !pats || npat < 1 || want < 0 || want > 2) return 0;
+   for (int k = 0; k < npat; k++) {
+      if (!pats[k]) return 0;
+      if (pats[k]->device != s->device) {
+         snprintf(g_last_error, sizeof g_last_error, "pattern lives on device %d, scan context on device %d", pats[k]->device, s->device);
+         return 0;
+      }
+   }
+   return !((options & SEEQDEV_FASTQ) && (options & (SEEQDEV_FASTA | SEEQDEV_SINGLELINE | MASK_INPUT)));
 }
 
 /* Everything of a run before its launches: arguments, fall-back flags, the optimistic workspace (hit lines: one line in
@@ -1992,14 +1354,8 @@ extern "C" int seeqdevScanRun(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, c
 static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const void *d_text, size_t nbytes, int options, int want, int hl_div)
 {
    seeqerr = 0;
-   if (!s || !pat || (!d_text && nbytes) || want < 0 || want > 2) { errno = EINVAL; return -1; }
-   if (pat->device != s->device) {
-      snprintf(g_last_error, sizeof g_last_error, "pattern lives on device %d, scan context on device %d", pat->device, s->device);
-      errno = EINVAL;
-      return -1;
-   }
+   if (!scan_args_ok(s, &pat, 1, options, want) || (!d_text && nbytes)) { errno = EINVAL; return -1; }
    const bool fastq = (options & SEEQDEV_FASTQ) != 0;
-   if (fastq && (options & (SEEQDEV_FASTA | SEEQDEV_SINGLELINE | MASK_INPUT))) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
    s->fastq = fastq; s->fq_done = false; s->fq_want = want;
    if (fastq) {
@@ -2042,6 +1398,15 @@ static int scan_setup(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const voi
       s->avg_text = d_text;
       s->avg_nbytes = nbytes;
    }
+   return 0;
+}
+
+extern "C" int seeqdevScanRun(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const void *d_text, size_t nbytes,
+                              int options, int want)
+{
+   if (scan_setup(s, pat, d_text, nbytes, options, want, SEEQ_HL_DIV)) return -1;
+   if (dispatch_run(s)) return -1;
+   s->ran = true;
    return 0;
 }
 
@@ -2196,10 +1561,9 @@ extern "C" int seeqdevScanCopyRecords(seeqdev_scan_t *s, seeqdev_hit_t *host_out
 extern "C" int seeqdevScanPacked(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const seeqdev_packed_t *batch, int options, int want)
 {
    seeqerr = 0;
-   if (!s || !pat || !batch || want < 0 || want > 2 || (batch->nreads && !batch->bases)) { errno = EINVAL; return -1; }
+   if (!scan_args_ok(s, &pat, 1, options, want) || !batch || (batch->nreads && !batch->bases)) { errno = EINVAL; return -1; }
    if (batch->read_len < 1 || batch->read_len > 256 || batch->stride < (batch->read_len + 3) / 4 ||
        (batch->nmask && batch->nstride < (batch->read_len + 7) / 8) || (options & (MASK_INPUT | SEEQDEV_FASTA | SEEQDEV_SINGLELINE | SEEQDEV_FASTQ))) { errno = EINVAL; return -1; }
-   if (pat->device != s->device) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
    s->fastq = false;
    seeqdev_pattern *mp = const_cast<seeqdev_pattern *>(pat);
@@ -2279,123 +1643,7 @@ extern "C" long seeqdevPackReads(const char *text, size_t nbytes, uint32_t read_
    return r;
 }
 
-/* Page-locked host memory for staging buffers (H2D at link speed instead of through a bounce buffer). */
-extern "C" void *seeqdevHostAlloc(size_t bytes)
-{
-   /* Called from seeqFileMatch's READER THREAD (seeq_file.c slot_reserve): seeqerr is the reference's plain global (libseeq.h:38) and belongs to the
-      caller's thread -- this entry reports through errno (thread-local) alone; seeq_file.c clears seeqerr where it hands the failure to the caller. */
-   void *p = NULL;
-   hipError_t e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocPortable);      /* every device may copy from it */
-   if (e != hipSuccess) { snprintf(g_last_error, sizeof g_last_error, "hipHostMalloc: %s", hipGetErrorString(e)); errno = ENOMEM; return NULL; }
-   return p;
-}
-
-extern "C" void seeqdevHostFree(void *p)
-{
-   if (p) (void)hipHostFree(p);
-}
-
-/* A context borrowed for scans of patterns it does not own: nothing of them is left to fetch, re-run or copy */
-static void scan_forget(seeqdev_scan *s)
-{
-   s->pat = nullptr;
-   s->ran = false;
-   memset(&s->counts, 0, sizeof s->counts);
-}
-
-/* Device memory for RESIDENT TEXT, chosen by measurement.  The scan kernel's time follows the physical pages a buffer gets from the driver
- * (0.77 / 0.87 / 0.92 ms per 3.75 GiB for the same text, stable for the life of the allocation; power-of-two blocks are fast far more often
- * than requests of an odd size: DESIGN.md section 5 (i)-(l)), so a caller that keeps text resident chooses its buffer once: up to twelve
- * candidate allocations (the plain one, then blocks of p bytes, p = the power of two >= bytes), each filled with synthetic reads and
- * scanned twice with the benchmark pattern; the one whose scan kernel was fastest is returned, the
- * others are freed.  probe_ms (may be NULL): the candidates' scan-kernel times, *nprobed of them.  The buffer's contents are undefined. */
-extern "C" void *seeqdevTextAllocFor(seeqdev_scan_t *scan, size_t bytes, int candidates, seeqdev_textinfo_t *info)
-{
-   seeqerr = 0;
-   if (info) memset(info, 0, sizeof *info);
-   if (bytes == 0) bytes = 1;
-   void *blk[12] = {nullptr};
-   size_t blk_bytes[12] = {0};
-   float ms[12] = {0};
-   int n = 0;
-   if (candidates > 12) candidates = 12;
-   if (candidates < 2 || bytes < ((size_t)64 << 20)) candidates = 1;      /* (nothing to tell apart on a scan of microseconds) */
-   size_t p2 = 1;
-   while (p2 < bytes) p2 <<= 1;
-   /* what the probing scan context allocates beside the candidates (reserve_impl for one segment of `bytes`: per-line, per-hit-line, per-tile arrays
-      and the records: about 0.46 bytes per text byte of a segment), kept free while the candidates are taken */
-   seeqdev_scan_t *sc = nullptr;
-   const size_t seg = bytes < (size_t)0xF0000000u ? bytes : (size_t)0xF0000000u;
-   const size_t headroom = seg / 2 + ((size_t)256 << 20);
-   size_t peak = 0;
-   for (int i = 0; i < candidates; i++) {
-      size_t want = bytes;
-      if (i > 0) {
-         want = p2;
-         size_t freeb = 0, total = 0;
-         if (hipMemGetInfo(&freeb, &total) != hipSuccess) break;
-         if (want + headroom > freeb) { want = bytes; if (want + headroom > freeb) break; }
-      }
-      if (hipMalloc(&blk[n], want) != hipSuccess) { (void)hipGetLastError(); blk[n] = nullptr; break; }
-      blk_bytes[n] = want;
-      peak += want;
-      n++;
-   }
-   if (n == 0) { hip_fail(hipErrorOutOfMemory, "seeqdevTextAlloc", ENOMEM); return NULL; }
-   int best = 0;
-   if (n > 1) {
-      static const char plain[] = "GATGTAGCGCGATTAGCCTG";
-      char keys[20];
-      for (int i = 0; i < 20; i++) keys[i] = plain[i] == 'A' ? 1 : plain[i] == 'C' ? 2 : plain[i] == 'G' ? 4 : 8;
-      seeqdev_pattern_t *pat = seeqdevPatternNew(keys, 20, 3);
-      /* Round 5: the launch time is a property of the PAIR (text buffer, scan context's workspace) -- the same text runs at 0.72 or 0.84 ms with
-         two contexts of one process, reproducibly (profiles/r05/workspace_probe.txt) -- so a caller that scans the text with a context of its own
-         (`scan`: reserve it first, so that its workspace is the one that stays) has the candidates probed with THAT context, and is left with no scan to fetch;
-         NULL: a context made here. */
-      sc = pat ? (scan ? scan : seeqdevScanNew(NULL)) : NULL;
-      const bool own_sc = scan == nullptr;
-      const bool prof_was = sc ? sc->prof : false;
-      const uint64_t nreads = bytes / 151;
-      bool ok = pat && sc && nreads > 0 && seeqdevScanSetProfiling(sc, 1) == 0;
-      for (int i = 0; ok && i < n; i++) {
-         ok = seeqdevSynthReads(blk[i], 0, nreads, 150, plain, 20, 3, 0x5EE92025ull, NULL) == 0 && hipStreamSynchronize(NULL) == hipSuccess;
-         for (int rep = 0; ok && rep < 2; rep++) {
-            seeqdev_counts_t cnt;
-            ok = seeqdevScanRun(sc, pat, blk[i], (size_t)nreads * 151, SQ_BEST, SEEQDEV_WANT_COUNTLINES) == 0 && seeqdevScanFetch(sc, &cnt) == 0;
-         }
-         float t[4] = {0, 0, 0, 0};
-         if (ok) ok = seeqdevScanLastTimes(sc, t) == 0;
-         ms[i] = t[1];
-      }
-      if (sc && own_sc) seeqdevScanFree(sc);
-      else if (sc) { (void)seeqdevScanSetProfiling(sc, prof_was ? 1 : 0); scan_forget(sc); }
-      if (pat) seeqdevPatternFree(pat);
-      if (ok) {
-         for (int i = 1; i < n; i++) if (ms[i] < ms[best]) best = i;
-         if (info) { for (int i = 0; i < n; i++) info->probe_ms[i] = ms[i]; info->nprobed = n; }
-      }                                                     /* (a failed probe: the plain allocation, nprobed = 0) */
-      for (int i = 0; i < n; i++) if (i != best) (void)hipFree(blk[i]);
-      seeqerr = 0;
-   }
-   if (info) { info->chosen = best; info->allocated_bytes = blk_bytes[best]; info->probe_peak_bytes = n > 1 ? peak + headroom : peak; }
-   return blk[best];
-}
-
-extern "C" void *seeqdevTextAllocInfo(size_t bytes, int candidates, seeqdev_textinfo_t *info) { return seeqdevTextAllocFor(NULL, bytes, candidates, info); }
-
-extern "C" void *seeqdevTextAlloc(size_t bytes, int candidates, float *probe_ms, int *nprobed)
-{
-   seeqdev_textinfo_t info;
-   void *p = seeqdevTextAllocInfo(bytes, candidates, &info);
-   if (nprobed) *nprobed = p ? info.nprobed : 0;
-   if (p && probe_ms) for (int i = 0; i < info.nprobed; i++) probe_ms[i] = info.probe_ms[i];
-   return p;
-}
-
-extern "C" void seeqdevTextFree(void *d_text)
-{
-   if (d_text) (void)hipFree(d_text);
-}
+#include "seeq_text_alloc.h"
 
 extern "C" int seeqdevScanCopyOffsets(seeqdev_scan_t *s, uint64_t *host_out, size_t first, size_t n)
 {
@@ -2460,410 +1708,8 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
    return seeqdevScanFetch(s, counts);
 }
 
-/* ========================================================================== */
-/* Several patterns, one text (barcode demultiplexing: reference doc/response.tex:358-360)  */
-/* ========================================================================== */
-/* Several patterns over one text.  ONE walk for all of them when the set has a union automaton and the text is k_pair's
- * (read-length lines, SQ_FAIL / SQ_CONVERT; seeq_multi.h) -- else, and under SEEQ_MULTI=sequential, a scan per pattern over
- * the resident text, back to back on the context's stream.  Per pattern: counts, and for SEEQDEV_WANT_RECORDS its ordered
- * records, kept on the host until the next multi scan.  Either way the results are those of a scan of each pattern alone. */
-static int multi_grow_host(seeqdev_scan_t *s, size_t n)
-{
-   if (s->multi_nrec + n > s->cap_multi_rec) {             /* page-locked: the records of a barcode set are hundreds of MB, and a pageable copy runs at a fifth of the link */
-      const size_t cap = (s->multi_nrec + n) + ((s->multi_nrec + n) >> 1) + 1024;
-      seeqdev_hit_t *g = nullptr;
-      if (hipHostMalloc((void **)&g, cap * sizeof *g, hipHostMallocDefault) != hipSuccess || !g) { errno = ENOMEM; return -1; }
-      if (s->multi_rec) {
-         if (hipStreamSynchronize(s->stream) != hipSuccess) { (void)hipHostFree(g); errno = EIO; return -1; }      /* (copies into the old buffer may be in flight) */
-         if (s->multi_nrec) memcpy(g, s->multi_rec, s->multi_nrec * sizeof *g);
-         (void)hipHostFree(s->multi_rec);
-      }
-      s->multi_rec = g;
-      s->cap_multi_rec = cap;
-   }
-   return 0;
-}
-
-static int demux_one_walk(seeqdev_scan_t *s, int npat, uint64_t capR);
-
-/* 0: done; 1: not for this set / text / options (the caller scans pattern by pattern); -1: error.  demux: the records stay on
-   the device and are demultiplexed there (seeqdevScanRunDemux) instead of going to the host. */
-static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *d_text, size_t nbytes,
-                          int options, int want, seeqdev_counts_t *counts, bool demux = false)
-{
-   const char *env = getenv("SEEQ_MULTI");
-   if (env && !strcmp(env, "sequential")) return 1;
-   if (npat < 2 || npat > SEEQ_MULTI_MAX || nbytes == 0) return 1;
-   const int nd = options & MASK_NONDNA;
-   if ((options & (MASK_INPUT | SEEQDEV_SINGLELINE)) || !(nd == SQ_FAIL || nd == SQ_CONVERT)) return 1;
-   for (int k = 0; k < npat; k++) if (!pats[k] || pats[k]->device != s->device) return 1;
-   if (use_device(s->device)) return -1;
-   MultiPlan *mp = multi_plan_for(&s->mplan, pats, npat);
-   if (!mp) { errno = ENOMEM; return -1; }
-   if (mp->state != 1) return 1;
-   /* the patterns' EQ tables of the exact pass (as run_segments makes the one of a single pattern) */
-   if (mp->eq_options != options) {
-      uint32_t *h = (uint32_t *)calloc((size_t)npat * 1536, sizeof(uint32_t));
-      if (!h) { errno = ENOMEM; return -1; }
-      for (int k = 0; k < npat; k++) eq_fill(h + (size_t)k * 1536, pats[k], options, mp->fw[k]);
-      const hipError_t e = hipMemcpy(mp->d_eq, h, (size_t)npat * 1536 * sizeof(uint32_t), hipMemcpyHostToDevice);
-      free(h);
-      if (e != hipSuccess) return hip_fail(e, "hipMemcpy(EQ tables)", EIO);
-      mp->eq_options = options;
-   }
-   if (scan_setup(s, &mp->upat, d_text, nbytes, options, want, SEEQ_HL_DIV_MULTI)) return -1;
-   s->multi_active = true;
-   int rc = -1;
-   for (int run = 0;; run++) {
-      if (multi_ws_ensure(s, npat)) break;
-      if (hipMemsetAsync(s->d_mcnt, 0, SEEQ_MULTI_MAX * sizeof(Counters), s->stream) != hipSuccess) { errno = EIO; break; }
-      const int r = dispatch_run(s);
-      if (r == -2) { rc = 1; break; }
-      if (r) break;
-      if (hipMemcpyAsync(s->h_mcnt, s->d_mcnt, (size_t)npat * sizeof(Counters), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-          hipStreamSynchronize(s->stream) != hipSuccess) { errno = EIO; break; }
-      const int next = rerun_next(s, run, *s->h_cnt, s->h_mcnt, npat);
-      if (next == 1) continue;
-      if (next == 2) rc = 1;                                /* not k_pair's text after all: a scan per pattern */
-      if (next == 0) {
-         /* results: counts, then every pattern's records from its region */
-         const uint64_t capR = s->cap_records / (uint64_t)npat;
-         if (demux) {
-            rc = demux_one_walk(s, npat, capR) ? -1 : 0;
-            if (rc == 0) s->last_multi = 1;
-            break;
-         }
-         s->multi_nrec = 0;
-         rc = 0;
-         if (want == SEEQDEV_WANT_RECORDS) {
-            size_t total = 0;
-            for (int k = 0; k < npat; k++) total += (size_t)s->h_mcnt[k].records;
-            if (multi_grow_host(s, total)) { rc = -1; break; }
-         }
-         for (int k = 0; k < npat && rc == 0; k++) {
-            const Counters &h = s->h_mcnt[k];
-            s->multi_cnt[k] = counts_of(h);
-            s->multi_first[k] = s->multi_nrec;
-            const size_t n = want == SEEQDEV_WANT_RECORDS ? (size_t)h.records : 0;
-            if (n) {
-               if (multi_grow_host(s, n)) { rc = -1; break; }
-               if (hipMemcpyAsync(s->multi_rec + s->multi_nrec, s->records + (uint64_t)k * capR, n * sizeof(seeqdev_hit_t), hipMemcpyDeviceToHost, s->stream) != hipSuccess) { errno = EIO; rc = -1; break; }
-               s->multi_nrec += n;
-            }
-            if (counts) counts[k] = s->multi_cnt[k];
-         }
-         if (rc == 0 && hipStreamSynchronize(s->stream) != hipSuccess) { errno = EIO; rc = -1; }
-         if (rc == 0) { s->multi_first[npat] = s->multi_nrec; s->multi_n = npat; s->last_multi = 1; }
-      }
-      break;
-   }
-   s->multi_active = false;
-   s->ran = false;                                         /* (seeqdevScanFetch has nothing to fetch: the multi scan is complete) */
-   return rc;
-}
-
-extern "C" int seeqdevScanRunMulti(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *d_text, size_t nbytes,
-                                   int options, int want, seeqdev_counts_t *counts)
-{
-   seeqerr = 0;
-   if (!s || !pats || npat < 1 || (!d_text && nbytes) || want < 0 || want > 2 || (options & SEEQDEV_FASTQ)) { errno = EINVAL; return -1; }
-   if (npat > s->cap_multi_n) {
-      seeqdev_counts_t *c = (seeqdev_counts_t *)realloc(s->multi_cnt, (size_t)npat * sizeof *c);
-      if (c) s->multi_cnt = c;
-      size_t *f = (size_t *)realloc(s->multi_first, ((size_t)npat + 1) * sizeof *f);
-      if (f) s->multi_first = f;
-      if (!c || !f) { errno = ENOMEM; return -1; }
-      s->cap_multi_n = npat;
-   }
-   s->multi_n = 0;
-   s->multi_nrec = 0;
-   s->last_multi = 0;
-   {
-      const int r = multi_one_pass(s, pats, npat, d_text, nbytes, options, want, counts);
-      if (r <= 0) return r;
-   }
-   s->multi_nrec = 0;
-   for (int k = 0; k < npat; k++) {
-      if (seeqdevScanRun(s, pats[k], d_text, nbytes, options, want)) return -1;
-      if (seeqdevScanFetch(s, &s->multi_cnt[k])) return -1;
-      s->multi_first[k] = s->multi_nrec;
-      const size_t n = want == SEEQDEV_WANT_RECORDS ? (size_t)s->multi_cnt[k].nrecords : 0;
-      if (n) {
-         if (multi_grow_host(s, n)) return -1;
-         if (seeqdevScanCopyRecords(s, s->multi_rec + s->multi_nrec, 0, n)) return -1;
-         s->multi_nrec += n;
-      }
-      if (counts) counts[k] = s->multi_cnt[k];
-   }
-   s->multi_first[npat] = s->multi_nrec;
-   s->multi_n = npat;
-   return 0;
-}
-
-/* 1: the last multi scan walked the text once for all its patterns; 0: a scan per pattern. */
-extern "C" int seeqdevScanLastMulti(const seeqdev_scan_t *s) { return s ? s->last_multi : 0; }
-
-extern "C" int seeqdevScanHostMulti(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const char *host_text, size_t nbytes,
-                                    int options, int want, seeqdev_counts_t *counts)
-{
-   seeqerr = 0;
-   if (!s || !pats || npat < 1 || (!host_text && nbytes) || (options & SEEQDEV_FASTQ)) { errno = EINVAL; return -1; }
-   if (use_device(s->device)) return -1;
-   if (text_upload(s, host_text, nbytes, false)) return -1;      /* once, for all patterns */
-   return seeqdevScanRunMulti(s, pats, npat, s->d_text, nbytes, options, want, counts);
-}
-
-extern "C" int seeqdevScanMultiRecords(const seeqdev_scan_t *s, int k, const seeqdev_hit_t **rec, size_t *nrec)
-{
-   if (!s || !rec || !nrec || k < 0 || k >= s->multi_n) { errno = EINVAL; return -1; }
-   *rec = s->multi_rec + s->multi_first[k];
-   *nrec = s->multi_first[k + 1] - s->multi_first[k];
-   return 0;
-}
-
-/* ========================================================================== */
-/* Demultiplexing: per line the best pattern of a set, on the device (seeq_demux.h)  */
-/* ========================================================================== */
-/* Per-line workspace for nkeys lines (8 bytes per line; allocated by the first demux of a context), keys cleared. */
-static int demux_ws_lines(seeqdev_scan *s, size_t nkeys)
-{
-   if (ws_make(&s->ws, {{s->d_dmcnt, sizeof(DemuxCnt)}, {s->h_dmcnt, sizeof(DemuxCnt), WS_PINNED}})) return -1;
-   if (ws_grow(&s->ws, &s->cap_dm_lines, nkeys, {{s->dm_key, nkeys * sizeof(uint32_t)}, {s->dm_aux, nkeys * sizeof(uint32_t)}})) return -1;
-   if (ensure_scan_ws(s, nkeys / SCAN_BLOCK + 2)) return -1;      /* block sums of the rank scan: the context's scan workspace */
-   if (nkeys) HIP_TRY(hipMemsetAsync(s->dm_key, 0, nkeys * sizeof(uint32_t), s->stream), EIO);
-   HIP_TRY(hipMemsetAsync(s->d_dmcnt, 0, sizeof(DemuxCnt), s->stream), EIO);
-   return 0;
-}
-
-/* Room for n output records; the first `keep` of the old area are carried over (the staging area of a scan per pattern grows). */
-static int demux_ws_out(seeqdev_scan *s, size_t n, size_t keep)
-{
-   if (n < 1) n = 1;
-   if (n <= s->cap_dm_out) return 0;
-   if (keep > s->cap_dm_out) keep = s->cap_dm_out;
-   uint4 *g = NULL;
-   const hipError_t e = hipMalloc((void **)&g, n * sizeof(uint4));
-   if (e != hipSuccess) { (void)hipGetLastError(); return hip_fail(e, "hipMalloc(demux records)", ENOMEM); }
-   if (keep && (hipMemcpyAsync(g, s->dm_out, keep * sizeof(uint4), hipMemcpyDeviceToDevice, s->stream) != hipSuccess ||
-                hipStreamSynchronize(s->stream) != hipSuccess)) {
-      (void)hipFree(g);
-      snprintf(g_last_error, sizeof g_last_error, "hipMemcpyAsync(demux staging)");
-      errno = EIO;
-      return -1;
-   }
-   if (s->dm_out) (void)hipFree(s->dm_out);
-   s->dm_out = g;
-   s->cap_dm_out = n;
-   return 0;
-}
-
-static void demux_fold(seeqdev_scan *s, const seeqdev_hit_t *rec, size_t n, int k, bool stage, uint32_t nkeys)
-{
-   const unsigned grid = (unsigned)((n + DEMUX_WG - 1) / DEMUX_WG);
-   if (stage)
-      hipLaunchKernelGGL(k_demux_fold<true>, dim3(grid), dim3(DEMUX_WG), 0, s->stream, (const uint4 *)rec, (uint32_t)n, (uint32_t)k, s->dm_key,
-                         s->dm_aux, nkeys, s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
-   else
-      hipLaunchKernelGGL(k_demux_fold<false>, dim3(grid), dim3(DEMUX_WG), 0, s->stream, (const uint4 *)rec, (uint32_t)n, (uint32_t)k, s->dm_key,
-                         s->dm_aux, nkeys, s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
-}
-
-/* After the folds: counts, ranks, the records in line order (src: the one walk's records; NULL: the staging area of a scan per
-   pattern), the counters to the host. */
-static int demux_finish(seeqdev_scan *s, uint32_t nkeys, int npat, const DemuxSrc *src, uint32_t nmax)
-{
-   const hipStream_t st = s->stream;
-   const bool stage = src == NULL;
-   if (nkeys) {
-      unsigned grid = (unsigned)((nkeys + DEMUX_WG * 8 - 1) / (DEMUX_WG * 8));
-      if (grid > (unsigned)s->ncu * 8) grid = (unsigned)s->ncu * 8;
-      if (stage) {
-         hipLaunchKernelGGL(k_demux_tally<true>, dim3(grid), dim3(DEMUX_WG), 0, st, (const uint32_t *)s->dm_key, (const uint32_t *)s->dm_aux, nkeys,
-                            s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
-         /* ranks in place of the keys; the records go to the record workspace (free: the last scan's records are folded) */
-         launch_scan<2>(s, st, s->dm_key, s->dm_key, nkeys, nullptr, nkeys, 0, &s->d_dmcnt->nassigned);
-         if (s->cap_records < s->cap_dm_out) {
-            HIP_TRY(hipStreamSynchronize(st), EIO);
-            if (reserve_impl(s, 0, 0, 0, s->cap_dm_out)) return -1;
-         }
-         hipLaunchKernelGGL(k_demux_scatter, dim3(grid), dim3(DEMUX_WG), 0, st, (const uint4 *)s->dm_out, (uint32_t)s->cap_dm_out,
-                            (const uint32_t *)s->dm_key, nkeys, (uint4 *)s->records, (uint32_t)s->cap_records, s->d_dmcnt);
-      } else {
-         hipLaunchKernelGGL(k_demux_tally<false>, dim3(grid), dim3(DEMUX_WG), 0, st, (const uint32_t *)s->dm_key, (const uint32_t *)s->dm_aux, nkeys,
-                            s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
-         launch_scan<2>(s, st, s->dm_key, s->dm_aux, nkeys, nullptr, nkeys, 0, &s->d_dmcnt->nassigned);
-         if (nmax)
-            hipLaunchKernelGGL(k_demux_emit, dim3((nmax + DEMUX_WG - 1) / DEMUX_WG, (unsigned)npat), dim3(DEMUX_WG), 0, st, *src,
-                               (const uint32_t *)s->dm_key, (const uint32_t *)s->dm_aux, nkeys, s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
-      }
-      HIP_TRY(hipGetLastError(), EIO);
-   }
-   HIP_TRY(hipMemcpyAsync(s->h_dmcnt, s->d_dmcnt, sizeof(DemuxCnt), hipMemcpyDeviceToHost, st), EIO);
-   HIP_TRY(hipStreamSynchronize(st), EIO);
-   const DemuxCnt &h = *s->h_dmcnt;
-   if (h.bad || h.nassigned > s->cap_dm_out || (stage && h.slot != h.nassigned)) {
-      snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the demultiplexer (flags %u, %u assigned, %u staged)", h.bad, h.nassigned, h.slot);
-      errno = EIO;
-      return -1;
-   }
-   if (stage && h.nassigned) {
-      HIP_TRY(hipMemcpyAsync(s->dm_out, s->records, (size_t)h.nassigned * sizeof(uint4), hipMemcpyDeviceToDevice, st), EIO);
-      HIP_TRY(hipStreamSynchronize(st), EIO);
-   }
-   s->dm_nrec = h.nassigned;
-   return 0;
-}
-
-/* The one walk is done: pattern k's h_mcnt[k].records records are at records + k * capR, in line order. */
-static int demux_one_walk(seeqdev_scan_t *s, int npat, uint64_t capR)
-{
-   const uint64_t nl = s->h_mcnt[0].lines;
-   if (nl > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
-   const uint32_t nkeys = (uint32_t)nl;
-   s->dm_nlines = nl;
-   if (demux_ws_lines(s, nkeys)) return -1;
-   DemuxSrc src;
-   memset(&src, 0, sizeof src);
-   src.rec = (const uint4 *)s->records;
-   src.stride = capR;
-   size_t total = 0;
-   uint32_t nmax = 0;
-   for (int k = 0; k < npat; k++) {
-      const uint32_t n = (uint32_t)s->h_mcnt[k].records;
-      src.n[k] = n;
-      total += n;
-      if (n > nmax) nmax = n;
-   }
-   if (demux_ws_out(s, total < nkeys ? total : nkeys, 0)) return -1;
-   for (int k = 0; k < npat; k++)
-      if (src.n[k]) demux_fold(s, s->records + (uint64_t)k * capR, src.n[k], k, false, nkeys);
-   return demux_finish(s, nkeys, npat, &src, nmax);
-}
-
-/* A scan per pattern: each pattern's records are folded on the device before the next scan overwrites them. */
-static int demux_per_pattern(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *d_text, size_t nbytes, int options)
-{
-   uint32_t nkeys = 0;
-   size_t sumrec = 0;
-   for (int k = 0; k < npat; k++) {
-      seeqdev_counts_t c;
-      if (seeqdevScanRun(s, pats[k], d_text, nbytes, options, SEEQDEV_WANT_RECORDS)) return -1;
-      if (seeqdevScanFetch(s, &c)) return -1;
-      if (k == 0) {
-         if (c.nlines > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
-         nkeys = (uint32_t)c.nlines;
-         s->dm_nlines = c.nlines;
-         if (demux_ws_lines(s, nkeys)) return -1;
-      } else if (c.nlines != nkeys) {
-         snprintf(g_last_error, sizeof g_last_error, "demultiplexer: pattern %d counted %llu lines, pattern 0 %u", k, (unsigned long long)c.nlines, nkeys);
-         errno = EIO;
-         return -1;
-      }
-      if (!c.nrecords) continue;
-      const size_t staged = sumrec < nkeys ? sumrec : nkeys;       /* at most this many slots are handed out so far */
-      sumrec += (size_t)c.nrecords;
-      if (demux_ws_out(s, sumrec < nkeys ? sumrec : nkeys, staged)) return -1;
-      demux_fold(s, s->records, (size_t)c.nrecords, k, true, nkeys);
-      HIP_TRY(hipGetLastError(), EIO);
-      HIP_TRY(hipStreamSynchronize(s->stream), EIO);          /* the next scan may reallocate the records the fold reads */
-   }
-   return demux_finish(s, nkeys, npat, nullptr, 0);
-}
-
-/* SEEQDEV_FASTQ: the demultiplexer's records (one per assigned raw line, in line order) reduced to those of the sequence lines and
-   numbered by record -- the filter of seeq_fastq.h in its demux mode, whose tallies replace the counters of demux_finish.  The filter
-   never writes in place: its output comes back from the scratch with one device copy (dm_out has a capacity of its own and carries its
-   contents over when it grows, so it cannot be swapped with the scratch as the record arrays are). */
-static int demux_fastq(seeqdev_scan *s)
-{
-   s->dm_nlines = fastq_nlines(s->dm_nlines);
-   DemuxCnt &h = *s->h_dmcnt;
-   const size_t n = s->dm_nrec;
-   uint32_t kept = 0;
-   memset(h.per_pat, 0, sizeof h.per_pat);
-   h.ambiguous = 0;
-   if (n) {
-      if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
-      if (reserve_impl(s, 0, 0, 0, n)) return -1;
-      if (fastq_launch(s, s->dm_out, nullptr, (uint32_t)n, true)) return -1;
-      HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-      const FastqCnt &f = *s->h_fqcnt;
-      if (f.bad || f.kept > n) {
-         snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the FASTQ filter (flags %u, %u of %zu kept)", f.bad, f.kept, n);
-         errno = EIO;
-         return -1;
-      }
-      kept = f.kept;
-      if (kept) {
-         HIP_TRY(hipMemcpyAsync(s->dm_out, s->fq_rec, (size_t)kept * sizeof(uint4), hipMemcpyDeviceToDevice, s->stream), EIO);
-         HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-      }
-      for (int k = 0; k < 256; k++) h.per_pat[k] = f.per_pat[k];
-      h.ambiguous = f.ambiguous;
-   }
-   h.nassigned = kept;
-   s->dm_nrec = kept;
-   return 0;
-}
-
-static int demux_args_ok(const seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *text, size_t nbytes, int options,
-                         const seeqdev_demux_counts_t *sum)
-{
-   if (!s || !pats || npat < 1 || npat > SEEQ_DEMUX_MAX || (!text && nbytes) || !sum || (options & MASK_MATCH) >= SQ_ALL) return 0;
-   if ((options & SEEQDEV_FASTQ) && (options & (SEEQDEV_FASTA | SEEQDEV_SINGLELINE | MASK_INPUT))) return 0;
-   for (int k = 0; k < npat; k++) if (!pats[k]) return 0;
-   return 1;
-}
-
-extern "C" int seeqdevScanRunDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *d_text, size_t nbytes,
-                                   int options, seeqdev_demux_counts_t *sum, uint64_t *per_pattern)
-{
-   seeqerr = 0;
-   if (!demux_args_ok(s, pats, npat, d_text, nbytes, options, sum)) { errno = EINVAL; return -1; }
-   if (use_device(s->device)) return -1;
-   const bool fastq = (options & SEEQDEV_FASTQ) != 0;
-   const int opts = (options & ~(MASK_MATCH | SEEQDEV_FASTQ)) | SQ_BEST;      /* (the set's scans run unflagged: demux_fastq filters their result) */
-   if (fastq) s->fq_ws = true;
-   s->dm_nrec = 0;
-   s->dm_nlines = 0;
-   s->multi_n = 0;                                         /* (no multi results on the host: seeqdevScanMultiRecords refuses) */
-   s->multi_nrec = 0;
-   s->last_multi = 0;
-   int rc = multi_one_pass(s, pats, npat, d_text, nbytes, opts, SEEQDEV_WANT_RECORDS, nullptr, true);
-   if (rc == 1) rc = demux_per_pattern(s, pats, npat, d_text, nbytes, opts);
-   scan_forget(s);                                         /* (the patterns are the caller's) */
-   if (rc == 0 && fastq) rc = demux_fastq(s);
-   if (rc) { s->dm_nrec = 0; return -1; }
-   const DemuxCnt &h = *s->h_dmcnt;
-   sum->nlines = s->dm_nlines;
-   sum->nassigned = h.nassigned;
-   sum->nambiguous = h.ambiguous;
-   if (per_pattern) for (int k = 0; k < npat; k++) per_pattern[k] = h.per_pat[k];
-   return 0;
-}
-
-extern "C" int seeqdevScanHostDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const char *host_text, size_t nbytes,
-                                    int options, seeqdev_demux_counts_t *sum, uint64_t *per_pattern)
-{
-   seeqerr = 0;
-   if (!demux_args_ok(s, pats, npat, host_text, nbytes, options, sum)) { errno = EINVAL; return -1; }
-   if (use_device(s->device)) return -1;
-   if (text_upload(s, host_text, nbytes, false)) return -1;
-   return seeqdevScanRunDemux(s, pats, npat, s->d_text, nbytes, options, sum, per_pattern);
-}
-
-extern "C" const seeqdev_demux_t *seeqdevScanDemuxDevice(const seeqdev_scan_t *s) { return s ? (const seeqdev_demux_t *)s->dm_out : NULL; }
-
-extern "C" int seeqdevScanCopyDemux(seeqdev_scan_t *s, seeqdev_demux_t *host_out, size_t first, size_t n)
-{
-   seeqerr = 0;
-   if (!s || (!host_out && n) || first > s->dm_nrec || n > s->dm_nrec - first) { errno = EINVAL; return -1; }
-   if (n == 0) return 0;
-   if (use_device(s->device)) return -1;
-   HIP_TRY(hipMemcpyAsync(host_out, s->dm_out + first, n * sizeof(seeqdev_demux_t), hipMemcpyDeviceToHost, s->stream), EIO);
-   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-   return 0;
-}
+#include "seeq_multi_host.h"
+#include "seeq_demux_host.h"
 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {
@@ -2884,198 +1730,4 @@ extern "C" int seeqdevScanLastLaunchTimes(const seeqdev_scan_t *s, float *ms, in
    return (int)n;
 }
 
-/* ========================================================================== */
-/* One string, one launch: seeqStringMatch (reference libseeq.c:171-352)        */
-/* ========================================================================== */
-/* The per-string entry point is what the reference's Python module calls for every string (seeqmodule.c:858).  One
- * workgroup: all threads stage the string (read over the link from page-locked host memory when it is short, else
- * from HBM) and the tables into LDS; then the string's positions are shared out over the 256 threads: every thread
- * computes the capped scores of its positions from a fresh column started m + tau + 1 characters earlier (exact from
- * there on, as in k_stream), applies the acceptance rules -- which only look at the scores of a position and the two
- * before it (libseeq.c:277-331: emit = stop ? !latch : zero, latch = stop ? 1 : zero) -- and the emissions are compacted
- * in order (block scan) / reduced (first, best), starts recovered by their threads, count + records written straight
- * into page-locked host memory.  A single lane walking the string took 0.17 us per character (41 us per call at 150
- * characters, 15 of them launch + synchronisation).  Strings with skipped bytes (SQ_IGNORE, SQ_STREAM) or longer than
- * STRING_PAR_MAX keep the one-lane scan.  One launch, one stream synchronisation, no device allocation.  Long strings
- * in line mode take the batched scan instead (libseeq_api.c). */
-static constexpr uint32_t STRING_LDS_MAX = 48u * 1024;      /* strings up to this are staged in LDS */
-static constexpr uint32_t STRING_ZC_MAX = 4096;             /* ... and up to this read straight from host memory */
-static constexpr uint32_t STRING_PAR_MAX = 32768;           /* ... and up to this scanned by all threads (positions fit 16 bits; longer strings in line mode take the batched scan) */
-
-template <int W>
-__global__ __launch_bounds__(WG) void k_string(const uint8_t *text, uint32_t n, const uint32_t *peq, int m, int tau, int options,
-                                               uint32_t *out, uint32_t cap, uint32_t seq)
-{
-   extern __shared__ __align__(16) uint8_t s_text[];       /* n + 16 bytes when staged */
-   __shared__ uint32_t s_peq[10 * W];
-   __shared__ uint8_t s_lut[256];
-   const int Wp = (m + 31) >> 5;
-   for (int i = threadIdx.x; i < 10 * W; i += WG) {
-      const int dir = i / (5 * W), rem = i % (5 * W), cls = rem / W, w = rem % W;
-      s_peq[i] = w < Wp ? peq[(dir * 5 + cls) * Wp + w] : 0u;
-   }
-   for (int b = threadIdx.x; b < 256; b += WG) s_lut[b] = sq_class_of((uint32_t)b, options);
-   const bool staged = n <= STRING_LDS_MAX;
-   if (staged) {
-      /* 16 bytes per thread and round, all loads of a round in flight together (the link's latency is paid once per round) */
-      for (uint32_t o = threadIdx.x * 16; o < n; o += WG * 16) {
-         const sq_chunk16_t c = sq_load16(text, o, n);
-         *reinterpret_cast<uint4 *>(s_text + o) = make_uint4(c.w[0], c.w[1], c.w[2], c.w[3]);
-      }
-   }
-   __shared__ uint32_t s_first, s_skip, s_key, s_wave[WG / 64];
-   const bool par = n <= STRING_PAR_MAX;                  /* (=> staged) */
-   if (threadIdx.x == 0) { s_first = n; s_skip = 0; s_key = 0xFFFFFFFFu; }
-   __syncthreads();
-   if (par) {
-      /* the line ends at its first terminator (or at n: bytes beyond read as NUL); a skipped byte before it -> one lane */
-      for (uint32_t j = threadIdx.x; j < n; j += WG) if (s_lut[s_text[j]] == SQC_TERM) atomicMin(&s_first, j);
-      __syncthreads();
-      const uint32_t len = s_first;
-      for (uint32_t j = threadIdx.x; j < len; j += WG) if (s_lut[s_text[j]] == SQC_SKIP) s_skip = 1u;
-      __syncthreads();
-      if (!s_skip) {
-         const int match_opt = options & 3;
-         const uint32_t *peq_f = s_peq, *peq_r = s_peq + 5 * W;
-         uint16_t *ed = reinterpret_cast<uint16_t *>(s_text + (((size_t)n + 31) & ~(size_t)15));   /* per position: emitted distance + 1, or 0 */
-         const uint32_t P = len + 1;                      /* positions 0..len; the last one is the terminator's step */
-         const uint32_t B = (P + WG - 1) / WG;
-         const uint32_t j0 = threadIdx.x * B, j1 = j0 + B < P ? j0 + B : P;
-         const uint32_t cnt = j0 < P ? sq_emit_window<W>((const uint8_t *)s_text, len, j0, j1, peq_f, (const uint8_t *)s_lut, m, tau, ed) : 0u;
-         uint32_t total = 0, nh_par = 0;
-         const uint32_t excl = block_excl_scan(cnt, &total, s_wave);      /* (also orders the ed[] writes: barrier inside) */
-         sq_hit_t *rec = reinterpret_cast<sq_hit_t *>(out + 4);
-         if (match_opt == SQK_ALL) {
-            uint32_t idx = excl;
-            for (uint32_t j = j0; j < j1 && cnt; j++) {
-               if (!ed[j]) continue;
-               if (idx < cap) {
-                  sq_hit_t h;
-                  h.line = 1;
-                  h.start = sq_reverse_start<W>((const uint8_t *)s_text, j, (int)ed[j] - 1, peq_r, (const uint8_t *)s_lut, m, tau);
-                  h.end = j;
-                  h.dist = (uint32_t)ed[j] - 1u;
-                  rec[idx] = h;
-               }
-               idx++;
-            }
-            nh_par = total;
-         } else {
-            /* SQ_BEST: smallest distance, first position; SQ_FIRST / SQ_COUNT: first position */
-            for (uint32_t j = j0; j < j1 && cnt; j++)
-               if (ed[j]) { atomicMin(&s_key, (match_opt == SQK_BEST ? ((uint32_t)ed[j] - 1u) << 16 : 0u) | j); if (match_opt != SQK_BEST) break; }
-            __syncthreads();
-            const uint32_t key = s_key;
-            if (key != 0xFFFFFFFFu) {
-               const uint32_t j = key & 0xFFFFu;
-               if (j >= j0 && j < j1 && cap) {
-                  sq_hit_t h;
-                  h.line = 1;
-                  h.start = sq_reverse_start<W>((const uint8_t *)s_text, j, (int)ed[j] - 1, peq_r, (const uint8_t *)s_lut, m, tau);
-                  h.end = j;
-                  h.dist = (uint32_t)ed[j] - 1u;
-                  rec[0] = h;
-               }
-            }
-            nh_par = key != 0xFFFFFFFFu ? 1u : 0u;
-         }
-         /* records first (every writer fences), then the count, then the ticket the host spins on */
-         __threadfence_system();
-         __syncthreads();
-         if (threadIdx.x == 0) {
-            out[0] = nh_par;
-            __threadfence_system();
-            __hip_atomic_store(&out[1], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-         }
-         return;
-      }
-   }
-   if (threadIdx.x != 0) return;
-   const uint8_t *tp = staged ? (const uint8_t *)s_text : text;
-   const uint32_t nh = sq_scan_line<W, SQ_MODE_EMIT>(tp, (uint64_t)n, 0, (const uint32_t *)s_peq, (const uint32_t *)(s_peq + 5 * W),
-                                                     (const uint8_t *)s_lut, m, tau, options & 3, 1,
-                                                     reinterpret_cast<sq_hit_t *>(out + 4), cap);
-   out[0] = nh;
-   __threadfence_system();
-   __hip_atomic_store(&out[1], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-template <int W>
-static void launch_string(seeqdev_scan *s, const seeqdev_pattern *pat, const uint8_t *text, uint32_t n, int options, uint32_t cap, uint32_t seq)
-{
-   size_t lds = n <= STRING_LDS_MAX ? (((size_t)n + 31) & ~(size_t)15) : 0;
-   if (n <= STRING_PAR_MAX) lds += (2 * ((size_t)n + 2) + 15) & ~(size_t)15;        /* + per-position emissions */
-   if (lds > 48u * 1024)                                    /* beyond the default limit of dynamic LDS per workgroup (set per device: every time) */
-      (void)hipFuncSetAttribute((const void *)k_string<W>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-   hipLaunchKernelGGL(k_string<W>, dim3(1), dim3(WG), lds, s->stream, text, n, (const uint32_t *)pat->d_peq, pat->wlen, pat->tau,
-                      options, s->h_strout, cap, seq);
-}
-
-/* data[0..n): the string (no NUL needed; a NUL inside ends it as in the reference).  On return *rec points at the
- * hit records (left to right; context-owned page-locked memory, valid until the next call) and *nrec is their number. */
-extern "C" int seeqdevStringMatch(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const char *data, size_t n, int options,
-                                  const seeqdev_hit_t **rec, size_t *nrec)
-{
-   seeqerr = 0;
-   if (!s || !pat || (!data && n) || !rec || !nrec || (options & SEEQDEV_FASTQ)) { errno = EINVAL; return -1; }
-   if (n > 0xFFFF0000ull) { errno = E2BIG; return -1; }
-   if (use_device(s->device)) return -1;
-   if (!s->h_strout || !s->h_str) {
-      const size_t nrec0 = 256;                             /* records */
-      const bool first_out = !s->h_strout;
-      if (ws_make(&s->ws, {{s->h_strout, 16 + nrec0 * sizeof(seeqdev_hit_t), WS_COHERENT}, {s->h_str, STRING_ZC_MAX + 16, WS_PINNED}})) return -1;
-      if (first_out) s->cap_strout = nrec0;
-   }
-   const uint8_t *dtext;
-   if (n <= STRING_ZC_MAX) {
-      memcpy(s->h_str, data, n);
-      dtext = s->h_str;                                     /* page-locked host memory is device-visible at the same address */
-   } else {
-      if (text_ensure(s, n)) return -1;
-      HIP_TRY(hipMemcpyAsync(s->d_text, data, n, hipMemcpyHostToDevice, s->stream), EIO);
-      s->avg_text = NULL;
-      dtext = s->d_text;
-   }
-   const int W = pat->words;
-   for (int attempt = 0; attempt < 2; attempt++) {
-      const uint32_t cap = (uint32_t)s->cap_strout;
-      s->h_strout[0] = 0;
-      const uint32_t seq = ++s->str_seq ? s->str_seq : ++s->str_seq;      /* never 0 */
-      volatile uint32_t *ticket = s->h_strout + 1;
-      *ticket = 0;
-      if (W <= 1) launch_string<1>(s, pat, dtext, (uint32_t)n, options, cap, seq);
-      else if (W <= 2) launch_string<2>(s, pat, dtext, (uint32_t)n, options, cap, seq);
-      else if (W <= 4) launch_string<4>(s, pat, dtext, (uint32_t)n, options, cap, seq);
-      else if (W <= 8) launch_string<8>(s, pat, dtext, (uint32_t)n, options, cap, seq);
-      else launch_string<16>(s, pat, dtext, (uint32_t)n, options, cap, seq);
-      HIP_TRY(hipGetLastError(), EIO);
-      /* The kernel's last store is its ticket, into fine-grained page-locked memory: spinning on it is shorter than the
-         runtime's completion path (hipStreamSynchronize: ~8 us).  After 200 us (long strings, a failed launch) the runtime
-         takes over. */
-      {
-         struct timespec t0, t1;
-         clock_gettime(CLOCK_MONOTONIC, &t0);
-         unsigned spins = 0;
-         while (__atomic_load_n(ticket, __ATOMIC_ACQUIRE) != seq) {
-            if ((++spins & 63u) == 0) {
-               clock_gettime(CLOCK_MONOTONIC, &t1);
-               if ((t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec) > 200000L) break;
-            }
-         }
-         if (__atomic_load_n(ticket, __ATOMIC_ACQUIRE) != seq) HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-      }
-      const uint32_t nh = s->h_strout[0];
-      if (nh <= cap) {
-         *rec = reinterpret_cast<const seeqdev_hit_t *>(s->h_strout + 4);
-         *nrec = nh;
-         return 0;
-      }
-      /* SQ_ALL with more hits than the record buffer holds: grow it and scan again */
-      (void)hipHostFree(s->h_strout);
-      s->h_strout = NULL;
-      s->cap_strout = (size_t)nh + (nh >> 2) + 64;
-      HIP_TRY(hipHostMalloc((void **)&s->h_strout, 16 + s->cap_strout * sizeof(seeqdev_hit_t), hipHostMallocCoherent), ENOMEM);
-   }
-   errno = EIO;
-   return -1;
-}
+#include "seeq_string.h"

@@ -1,7 +1,7 @@
 /*
  * seeq_exact1.h -- k_exact1<MODE, W>: the exact pass for patterns of <= 30 (W = 1) / 31..62 (W = 2) positions.
  *
- * Same job as k_exact<1,*> (seeq_device.hip): over the HIT lines only, apply the reference's
+ * Same job as k_exact<1,*> (seeq_generic.h): over the HIT lines only, apply the reference's
  * acceptance rules (libseeq.c:277-331) and recover match starts (libseeq.c:289-316); but with the
  * top-aligned 12-op Myers step and the byte-indexed EQ tables of the scan kernels instead of the
  * generic multi-word column, and with the text staged per lane through LDS so that the per-character

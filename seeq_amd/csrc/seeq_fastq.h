@@ -8,7 +8,7 @@
  * 16-byte records -- with their 8-byte line offsets, where the scan made them -- keeps line numbers with
  * ((line - 1) & 3) == 1 and rewrites them to ((line - 1) >> 2) + 1.
  *
- * The three-launch scan shape of the project (k_scan_reduce / _top / _apply in seeq_device.hip), over tiles of
+ * The three-launch scan shape of the project (k_scan_reduce / _top / _apply in seeq_scan.h), over tiles of
  * SEEQ_FASTQ_TILE records:
  *
  *   k_fastq_reduce   per tile: records kept, and -- independent of the compaction -- kept records that OPEN a line (input

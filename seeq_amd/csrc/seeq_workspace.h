@@ -2,13 +2,16 @@
  * seeq_workspace.h -- who owns a scan context's buffers: the workspace of seeqdev_scan (seeq_device.hip) as PURE host code.
  *
  * A Workspace knows how memory of three kinds is had and given back (hooks: seeq_device.hip wraps hipMalloc / hipHostMalloc /
- * hipFree / hipHostFree, tests/host_harness.cpp wraps malloc and refuses the N-th request) and which member pointers of its
+ * hipFree / hipHostFree and its copies, tests/host_harness.cpp wraps malloc / memcpy and refuses the N-th request) and which member pointers of its
  * context hold a block (the registry: the address of the pointer and its kind -- a slot enters it the first time it is
- * grown, made or adopted).  Two guarantees:
+ * grown or made).  Three guarantees:
  *
  *   ws_grow   a capacity group grows COMPLETELY OR NOT AT ALL as far as its capacity says: per member, in the listed order, the new
  *             block first, then the old one goes; a refusal returns -1 with the capacity untouched and every slot on a live block
  *             at least as large as that capacity needs (a member may already be on its bigger block).
+ *   ws_grow_keep  ONE member that carries its first `keep` bytes over: the new block, the copy (hooks.copy), then the old block goes,
+ *             the capacity last; a refusal or a failed copy returns -1 with the new block released and the old one, its contents
+ *             and the capacity as they were.
  *   ws_make   fixed-size buffers made on first use, ALL OR NOTHING: a refusal releases what this call made and leaves those slots
  *             NULL -- a "made yet?" guard never sees half a set.
  *
@@ -28,6 +31,8 @@ struct WsHooks {
    void *(*alloc)(void *ctx, int kind, size_t bytes);      /* NULL: refused (the hook reports why) */
    void  (*release)(void *ctx, int kind, void *p);
    void  *ctx;
+   /* ws_grow_keep alone; != 0: failed (the hook reports why).  Last, so a table of alloc / release / ctx (a user of ws_grow and ws_make) needs none */
+   int   (*copy)(void *ctx, int kind, void *dst, const void *src, size_t bytes);
 };
 
 static constexpr int WS_MAX_SLOTS = 96;
@@ -52,8 +57,6 @@ static inline int ws_adopt(Workspace *w, void **slot, int kind)
    w->reg[w->nreg].slot = slot; w->reg[w->nreg].kind = kind;
    return w->nreg++;
 }
-/* ... for the buffers that carry their contents over when they grow (their growth copies and synchronises: written where it happens) */
-template <class T> static inline int ws_adopt(Workspace *w, T *&p, int kind) { return ws_adopt(w, (void **)&p, kind); }
 
 static inline int ws_grow(Workspace *w, size_t *cap, size_t want, std::initializer_list<WsMember> members)
 {
@@ -65,6 +68,19 @@ static inline int ws_grow(Workspace *w, size_t *cap, size_t want, std::initializ
       if (*m.slot) w->hooks.release(w->hooks.ctx, m.kind, *m.slot);
       *m.slot = g;
    }
+   *cap = want;
+   return 0;
+}
+
+static inline int ws_grow_keep(Workspace *w, size_t *cap, size_t want, WsMember m, size_t keep)
+{
+   if (want <= *cap) return 0;
+   if (ws_adopt(w, m.slot, m.kind) < 0) return -1;
+   void *g = w->hooks.alloc(w->hooks.ctx, m.kind, m.bytes);
+   if (!g) return -1;
+   if (*m.slot && keep && w->hooks.copy(w->hooks.ctx, m.kind, g, *m.slot, keep)) { w->hooks.release(w->hooks.ctx, m.kind, g); return -1; }
+   if (*m.slot) w->hooks.release(w->hooks.ctx, m.kind, *m.slot);
+   *m.slot = g;
    *cap = want;
    return 0;
 }

@@ -61,7 +61,7 @@ extern "C" long harness_scan(const uint8_t *text, size_t n, const char *keys, in
    return run<16>(text, n, keys, m, tau, options, mode, out, cap);
 }
 
-// seeqStringMatch as k_string computes it (seeq_device.hip): the positions of the line shared out in blocks of `block`
+// seeqStringMatch as k_string computes it (seeq_amd/csrc/seeq_string.h): the positions of the line shared out in blocks of `block`
 // (what the 256 threads of the workgroup get), each block from a fresh column through sq_emit_window, emissions then
 // taken in order (SQ_ALL), the first (SQ_FIRST) or the first with the smallest distance (SQ_BEST), starts by
 // sq_reverse_start.  Returns the number of hits, or -1 for a line the kernel leaves to its one-lane scan (a skipped
@@ -445,13 +445,18 @@ extern "C" int harness_plan(const char *keys, int m, int tau, int options, int w
 //        12 slots that were on a live block before the step and are not now
 //        13 members whose block is smaller than the last completed growth of their group asked for
 //      Returns the number of steps.
+//      harness_ws_keep: ONE slot through ws_grow_keep (the copy hook is memcpy and fails the N-th copy on demand): grown to 100 bytes from
+//      nothing, to 300 keeping 100, asked for 200 (nothing to do), to 1000 keeping 300, the same once more (what a caller does after a
+//      failure), free-all.  The block is filled with a byte pattern after every step; a row of 10 per step:
+//        0 rc   1 capacity before   2 after   3 requests so far   4 live blocks   5 bad releases   6 copies so far
+//        7 the bytes to keep hold the pattern (before the refill)   8 the slot is on the block it was on   9 bytes of its block (-1: none)
 #include "../seeq_amd/csrc/seeq_workspace.h"
 
 namespace {
 struct FakeMem {
    struct { void *p; size_t bytes; int kind; } live[128];
    int  nlive;
-   long requests, refuse_at, bad;
+   long requests, refuse_at, bad, copies, fail_copy_at;
    long size_of(const void *p) const { for (int i = 0; i < nlive; i++) if (live[i].p == p) return (long)live[i].bytes; return -1; }
 };
 void *fake_alloc(void *ctx, int kind, size_t bytes)
@@ -470,6 +475,14 @@ void fake_release(void *ctx, int kind, void *p)
    for (int i = 0; i < f->nlive; i++)
       if (f->live[i].p == p && f->live[i].kind == kind) { free(p); f->live[i] = f->live[--f->nlive]; return; }
    f->bad++;                                               // never handed out, handed back already, or of another kind
+}
+
+int fake_copy(void *ctx, int, void *dst, const void *src, size_t bytes)
+{
+   FakeMem *f = (FakeMem *)ctx;
+   if (++f->copies == f->fail_copy_at) return -1;
+   memcpy(dst, src, bytes);
+   return 0;
 }
 
 // a stand-in for seeqdev_scan: member pointers of several types, capacities beside them
@@ -527,7 +540,7 @@ extern "C" int harness_ws_script(long refuse_at, long long *rows, int max_rows)
    std::memset(&f, 0, sizeof f);
    std::memset(&c, 0, sizeof c);
    f.refuse_at = refuse_at;
-   c.ws.hooks = {fake_alloc, fake_release, &f};
+   c.ws.hooks = {fake_alloc, fake_release, &f, fake_copy};
    int ns = 0;
    for (const auto &st : steps) {
       if (ns == max_rows) break;
@@ -547,6 +560,37 @@ extern "C" int harness_ws_script(long refuse_at, long long *rows, int max_rows)
          for (int i = 0; i < c.ws.nreg; i++) if (*c.ws.reg[i].slot) held++;
       }
       r[0] = st.kind; r[1] = st.g; r[5] = (long long)st.n; r[6] = f.requests; r[7] = f.nlive; r[8] = held; r[9] = f.bad; r[12] = lost;
+   }
+   return ns;
+}
+
+extern "C" int harness_ws_keep(long refuse_at, long fail_copy_at, long long *rows, int max_rows)
+{
+   static const struct { size_t want, keep; } steps[] = {{100, 0}, {300, 100}, {200, 100}, {1000, 300}, {1000, 300}, {0, 0}};
+   FakeMem f;
+   std::memset(&f, 0, sizeof f);
+   f.refuse_at = refuse_at; f.fail_copy_at = fail_copy_at;
+   Workspace ws;
+   std::memset(&ws, 0, sizeof ws);
+   ws.hooks = {fake_alloc, fake_release, &f, fake_copy};
+   uint8_t *buf = NULL;
+   size_t cap = 0;
+   int ns = 0;
+   for (const auto &st : steps) {
+      if (ns == max_rows) break;
+      long long *r = rows + (size_t)10 * ns++;
+      const uint8_t *was = buf;
+      const size_t cap0 = cap;
+      const long had = was ? f.size_of(was) : 0;             // bytes that hold the pattern
+      int rc = 0;
+      if (st.want) rc = ws_grow_keep(&ws, &cap, st.want, {buf, st.want}, st.keep);
+      else ws_free_all(&ws);
+      int intact = 1;
+      for (size_t i = 0; buf && i < st.keep && (long)i < had; i++) intact &= buf[i] == (uint8_t)(i * 7 + 3);
+      const long size = buf ? f.size_of(buf) : -1;
+      for (long i = 0; i < size; i++) buf[i] = (uint8_t)(i * 7 + 3);
+      const long long v[10] = {rc, (long long)cap0, (long long)cap, f.requests, f.nlive, f.bad, f.copies, intact, buf == was, size};
+      for (int j = 0; j < 10; j++) r[j] = v[j];
    }
    return ns;
 }

@@ -1749,6 +1749,53 @@ def test_multi_pattern_workspace_growth(gpu, capi, oracle):
             p.close()
 
 
+def test_multi_records_on_the_host_grow_with_records_in_them(gpu, capi, oracle, monkeypatch):
+    """A scan per pattern (SEEQ_MULTI=sequential) on a FRESH context: pattern 0 leaves about 100 records on the host, pattern 1 about 3000 --
+    more than the first buffer's 1.5 x 100 + 1024 -- so the page-locked buffer grows with pattern 0's records in it; pattern 2 adds
+    about 100.  Every pattern's records are those of a scan of that pattern alone, and the oracle's."""
+    from seeq_amd import device as dev
+    rng = random.Random(31)
+    barcodes = ["GATTACAGACCA", "TTGACCGATAGG", "CCATGGTACATC"]
+    lines = []
+    for i in range(4000):
+        t = [rng.choice("ACGT") for _ in range(30)]
+        if i % 4:
+            t[0:12] = barcodes[1]
+        if i % 40 == 0:
+            t[9:21] = barcodes[0]
+        if i % 40 == 2:
+            t[16:28] = barcodes[2]
+        lines.append("".join(t))
+    buf = ("\n".join(lines) + "\n").encode()
+    pats = [dev.Pattern(b, 1) for b in barcodes]
+    monkeypatch.setenv("SEEQ_MULTI", "sequential")
+    sc, alone = dev.Scanner(), dev.Scanner()
+    got = sc.scan_host_multi(pats, buf, SQ_BEST, dev.WANT_RECORDS)
+    assert not sc.last_multi_one_pass()
+    n = [g["nrecords"] for g in got]
+    assert 90 <= n[0] <= 200 and n[1] >= 2900 and 90 <= n[2] <= 200 and n[0] + n[1] > n[0] + n[0] // 2 + 1024, n
+    for k, (b, p) in enumerate(zip(barcodes, pats)):
+        one = alone.scan_host(p, buf, SQ_BEST, dev.WANT_RECORDS)
+        assert got[k]["nrecords"] == one["nrecords"] == len(got[k]["records"]) and np.array_equal(got[k]["records"], one["records"]), k
+        exp = oracle.buffer_scan(b, 1, buf, SQ_BEST)
+        assert got[k]["nmatchlines"] == exp["nmatchlines"] and np.array_equal(got[k]["records"].astype(np.uint64), exp["records"]), k
+    sc.close()
+    alone.close()
+    for p in pats:
+        p.close()
+
+
+def test_string_match_record_buffer_grows_and_serves_the_next_string(gpu, capi, oracle):
+    """SQ_ALL with more hits than the context's first record buffer holds (256): the hits of `A` in 600 x A -- the buffer is grown and
+    the string scanned again -- then a short string with one hit on the same context.  Both: the oracle's hits."""
+    s = SQ(capi, "A", 0)
+    for text in ("A" * 600, "CCACC"):
+        exp = oracle.string_match("A", 0, text, SQ_ALL)
+        assert len(exp) > 256 if len(text) == 600 else len(exp) == 1
+        assert s.match(text, SQ_ALL) == exp, text[:8]
+    s.close()
+
+
 @pytest.mark.parametrize("m,k", [(42, 8), (42, 15), (34, 10), (27, 8), (20, 5), (20, 3), (27, 4), (34, 6), (42, 10)])
 def test_published_sweep_cells_small(gpu, capi, oracle, m, k):
     """The reference's published sweep (doc/response.tex:209-232: chromosome lines, m = 20 / 27 / 34 / 42 x k) at a size the oracle

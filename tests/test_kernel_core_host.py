@@ -855,6 +855,48 @@ def test_workspace_growth_is_grouped_and_every_refusal_leaves_it_whole(harness):
         assert {q["g"]: q["cap"] for q in rows if q["kind"] == GROW} == final_cap, n
 
 
+def test_a_buffer_grown_with_its_contents_keeps_them_or_stays_as_it_was(harness):
+    """ws_grow_keep (seeq_workspace.h) over the fake hooks (host_harness.cpp: harness_ws_keep): one slot grown 0 -> 100 -> 300 bytes (keeping
+    100), asked for 200, grown to 1000 (keeping 300), asked again, freed.  Clean: the kept bytes arrive, the old block goes exactly once (one
+    live block, no bad release), `want <= cap` asks for nothing.  Every request refused in turn, every copy failed in turn: -1, and slot,
+    block, contents and capacity are what they were, the new block is given back; the same call made again succeeds.  After ws_free_all every
+    block handed out has come back."""
+    import ctypes as C
+    H = harness
+    H.harness_ws_keep.restype = C.c_int
+    H.harness_ws_keep.argtypes = [C.c_long, C.c_long, C.c_void_p, C.c_int]
+    cols = ("rc", "cap0", "cap", "requests", "live", "bad", "copies", "intact", "same", "size")
+
+    def script(refuse_at, fail_copy_at):
+        rows = np.zeros((8, len(cols)), dtype=np.int64)
+        n = H.harness_ws_keep(refuse_at, fail_copy_at, rows.ctypes.data, 8)
+        assert n == 6
+        return [dict(zip(cols, (int(v) for v in row))) for row in rows[:n]]
+
+    clean = script(0, 0)
+    assert [r["rc"] for r in clean] == [0] * 6 and all(r["bad"] == 0 and r["intact"] == 1 for r in clean), clean
+    assert [(r["cap0"], r["cap"], r["size"]) for r in clean[:5]] == [(0, 100, 100), (100, 300, 300), (300, 300, 300), (300, 1000, 1000), (1000, 1000, 1000)]
+    assert [r["live"] for r in clean] == [1, 1, 1, 1, 1, 0]            # the old block went with every growth; free-all gave the last one back
+    assert [r["requests"] for r in clean] == [1, 2, 2, 3, 3, 3] and [r["copies"] for r in clean] == [0, 1, 1, 2, 2, 2]
+    assert [r["same"] for r in clean[:5]] == [0, 0, 1, 0, 1]           # want <= cap: nothing asked for, nothing copied, nothing moved
+    assert clean[5]["size"] == -1
+    for refuse_at, fail_copy_at in [(n, 0) for n in (1, 2, 3)] + [(0, n) for n in (1, 2)]:
+        rows = script(refuse_at, fail_copy_at)
+        tag = (refuse_at, fail_copy_at)
+        failed = [i for i, r in enumerate(rows) if r["rc"] != 0]
+        assert len(failed) == 1 and all(r["bad"] == 0 for r in rows), (tag, rows)
+        i = failed[0]
+        r, before = rows[i], (rows[i - 1] if i else dict(cap=0, size=-1, live=0))
+        assert r["rc"] == -1 and r["cap"] == r["cap0"] == before["cap"] and r["same"] == 1 and r["size"] == before["size"], (tag, r)
+        assert r["intact"] == 1 and r["live"] == before["live"], (tag, r)      # contents as they were; the new block (a failed copy) given back
+        assert r["requests"] == (refuse_at or before.get("requests", 0) + 1), (tag, r)
+        later = rows[i + 1:-1]
+        assert all(q["rc"] == 0 and q["intact"] == 1 for q in later), (tag, later)
+        if i in (1, 3):                                                # asked again (300: by the growth to 1000 that follows): it grows, contents kept
+            assert rows[4]["cap"] == 1000 and rows[4]["size"] == 1000 and rows[4]["live"] == 1, (tag, rows[4])
+        assert rows[-1]["live"] == 0 and rows[-1]["size"] == -1, (tag, rows[-1])
+
+
 # ---- the re-run policy (seeq_amd/csrc/seeq_rerun.h) over host_harness.cpp.  Every expected number below is written out from the arithmetic the
 #      host driver carried before the policy had a header of its own: a grown capacity is need + need // 8 + 64. ----
 OVF_LINES, OVF_HITLINES, OVF_RECORDS, OVF_NO_STREAM, OVF_NONDNA, OVF_LONG_LINES, OVF_BAD_ENTRY, OVF_SEAM, OVF_LEADER = 1, 2, 4, 8, 16, 32, 64, 128, 256
