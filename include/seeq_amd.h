@@ -77,6 +77,12 @@ typedef struct {
    uint32_t dist;
 } seeqdev_hit_t;
 
+/* A record of a both-strands scan (seeqdevScanRunStrands below) carries its strand in bit 31 of `dist` -- a distance never exceeds
+ * SEEQDEV_MAX_WLEN - 1 = 511, so the bit is free; every other scan leaves it clear. */
+#define SEEQDEV_HIT_MINUS 0x80000000u
+#define SEEQDEV_HIT_DIST(hit_dist)   ((hit_dist) & ~SEEQDEV_HIT_MINUS)           /* the distance of a record's `dist` word */
+#define SEEQDEV_HIT_STRAND(hit_dist) (((hit_dist) & SEEQDEV_HIT_MINUS) ? 1 : 0)   /* 0: the pattern as given (plus); 1: its reverse complement (minus) */
+
 typedef struct {
    uint64_t nlines;       /* counted lines (FASTA headers excluded)            */
    uint64_t nmatchlines;  /* lines with at least one hit                       */
@@ -249,12 +255,50 @@ typedef struct {
    uint64_t nambiguous;  /* of them, margin == 0 */
 } seeqdev_demux_counts_t;
 
+/* BOTH ORIENTATIONS of a barcode set: pass seeqdevPatternRevComp() members in the set beside the barcodes -- the winner's index then names
+ * the strand as well as the barcode (no strand bit in seeqdev_demux_t). */
 int seeqdevScanRunDemux (seeqdev_scan_t * scan, const seeqdev_pattern_t * const * pats, int npat, const void * d_text, size_t nbytes,
                          int options, seeqdev_demux_counts_t * sum, uint64_t * per_pattern);
 int seeqdevScanHostDemux(seeqdev_scan_t * scan, const seeqdev_pattern_t * const * pats, int npat, const char * host_text, size_t nbytes,
                          int options, seeqdev_demux_counts_t * sum, uint64_t * per_pattern);
 const seeqdev_demux_t * seeqdevScanDemuxDevice(const seeqdev_scan_t * scan);
 int seeqdevScanCopyDemux(seeqdev_scan_t * scan, seeqdev_demux_t * host_out, size_t first, size_t n);
+
+/* BOTH STRANDS IN ONE CALL.  Reads come off either strand: an adapter, primer or barcode occurs in a read as its reverse complement as
+ * often as forwards.  seeqdevPatternRevComp: the reverse complement of a compiled pattern -- the positions reversed, every class
+ * complemented member by member (A <-> T/U, C <-> G; N stays N) -- as a new caller-owned pattern on the same device with the same
+ * distance (seeqdevPatternFree).
+ * seeqdevScanRunStrands / seeqdevScanHostStrands: the text is scanned with `pat` (the PLUS strand) and with its reverse complement (MINUS;
+ * built by the pattern's first such call, kept in the handle and freed with it), each scan bit-exact with the reference as every scan
+ * here is, and the two record sets are merged ON THE DEVICE (seeq_strand.h):
+ *   SQ_ALL               every record of both, ordered by the 64-bit key line << 32 | end, plus before minus on a tie (`end` and not
+ *                        `start`: the records of a line have strictly increasing ends within a strand, while starts repeat);
+ *   SQ_BEST / SQ_FIRST   one record per matching line, the winner: the smaller dist / the smaller end, plus on a tie.
+ * A minus record has SEEQDEV_HIT_MINUS set in `dist` (SEEQDEV_HIT_DIST / SEEQDEV_HIT_STRAND); its start / end are positions in the line as
+ * scanned.  A self-complementary pattern (GAATTC) reports every SQ_ALL hit twice, plus then minus, and wins its ties as plus.
+ * counts: nlines / nheaders as either scan; nmatchlines = lines with a hit on either strand; nhits = merged hits; nrecords = merged
+ * records (SEEQDEV_WANT_RECORDS), else 0.  SEEQDEV_WANT_COUNTLINES / COUNTMATCH have nothing to merge: as under SEEQDEV_FASTQ they are
+ * scanned for records (SQ_FIRST / SQ_ALL; record workspace for every hit) and report nrecords = 0.  per_strand (may be NULL): [0] plus,
+ * [1] minus records of the result.  Synchronous.  Afterwards seeqdevScanRecordsDevice / CopyRecords / CopyOffsets serve the merged
+ * arrays, seeqdevScanFetch fails (EINVAL) until the next scan, and the context's next plain scan answers as on a fresh context.
+ * `options`: match mode, non-DNA mode, SEEQDEV_FASTA, SEEQDEV_FASTQ (the two scans run unflagged and the merged records go once through
+ * the filter: record numbering, nlines and offsets in the original buffer as documented above).  EINVAL, before any device call:
+ * SEEQDEV_SINGLELINE, an input-mode bit (SQ_STREAM), NULL scan / pat / counts, NULL text with bytes, `want` outside 0 .. 2, a pattern on
+ * another device.  E2BIG: more than 2^32 - 1 records to merge.
+ * How: the pair {pat, twin} in ONE walk over the text when the pattern is barcode-sized (8 .. 12 positions at distance <= 1) and the
+ * pair has a union automaton (as seeqdevScanRunMulti: read-length lines, SQ_FAIL / SQ_CONVERT), else -- and under SEEQ_MULTI=sequential -- two scans, the first one's records and offsets
+ * copied aside on the device (24 bytes per record); seeqdevScanLastMulti tells which.  The bytes are the same either way.  Device memory
+ * of its own (allocated by a context's first such call, freed with it): 24 bytes per record kept aside and per merged record.
+ * (The reference searches one orientation per run: an addition of this boundary.) */
+seeqdev_pattern_t * seeqdevPatternRevComp(const seeqdev_pattern_t * pat);
+int seeqdevScanRunStrands (seeqdev_scan_t * scan, const seeqdev_pattern_t * pat, const void * d_text,    size_t nbytes, int options, int want,
+                           seeqdev_counts_t * counts, uint64_t per_strand[2]);
+int seeqdevScanHostStrands(seeqdev_scan_t * scan, const seeqdev_pattern_t * pat, const char * host_text, size_t nbytes, int options, int want,
+                           seeqdev_counts_t * counts, uint64_t per_strand[2]);
+
+/* Device time (ms) of the last both-strands call's merge -- its kernels and device copies, between two HIP events on the context's stream
+ * (profiling on; 0 otherwise, and when there was nothing to merge). */
+int seeqdevScanLastStrandsMs(const seeqdev_scan_t * scan, float * merge_ms);
 
 /* PACKED READ BATCHES -- 2 bits per base instead of a byte: a quarter of the HBM (and PCIe) traffic of the ASCII scan for
  * read sets that are kept packed anyway (BAM, .2bit, a sequencer's own format).  Layout, all device pointers:

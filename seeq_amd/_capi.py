@@ -22,6 +22,7 @@ SQ_ANY, SQ_MATCH, SQ_NOMATCH, SQ_COUNTLINES, SQ_COUNTMATCH = 0, 1, 2, 3, 4
 # seeq_amd.h
 WANT_COUNTLINES, WANT_COUNTMATCH, WANT_RECORDS = 0, 1, 2
 SEEQDEV_FASTA, SEEQDEV_SINGLELINE, SEEQDEV_FASTQ = 0x100, 0x200, 0x400
+SEEQDEV_HIT_MINUS = 0x80000000      # bit 31 of a both-strands record's dist: the minus strand
 
 
 class match_t(C.Structure):
@@ -83,6 +84,7 @@ EXPORTS = [
     "seeqdevHostFree", "seeqdevStringMatch", "seeqdevScanHostBegin", "seeqdevScanLastCopyMs", "seeqdevPatternDevice",
     "seeqdevScanRunMulti", "seeqdevScanHostMulti", "seeqdevScanMultiRecords", "seeqdevScanLastMulti", "seeqdevScanPacked", "seeqdevPackReads", "seeqdevPackReadsDevice",
     "seeqdevScanRunDemux", "seeqdevScanHostDemux", "seeqdevScanDemuxDevice", "seeqdevScanCopyDemux",
+    "seeqdevPatternRevComp", "seeqdevScanRunStrands", "seeqdevScanHostStrands", "seeqdevScanLastStrandsMs",
 ]
 
 
@@ -214,6 +216,14 @@ def lib():
     L.seeqdevScanDemuxDevice.restype = C.c_void_p
     L.seeqdevScanCopyDemux.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
     L.seeqdevScanCopyDemux.restype = C.c_int
+    L.seeqdevPatternRevComp.argtypes = [C.c_void_p]
+    L.seeqdevPatternRevComp.restype = C.c_void_p
+    L.seeqdevScanRunStrands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(seeqdev_counts_t), C.POINTER(C.c_uint64)]
+    L.seeqdevScanRunStrands.restype = C.c_int
+    L.seeqdevScanHostStrands.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int, P(seeqdev_counts_t), C.POINTER(C.c_uint64)]
+    L.seeqdevScanHostStrands.restype = C.c_int
+    L.seeqdevScanLastStrandsMs.argtypes = [C.c_void_p, P(C.c_float)]
+    L.seeqdevScanLastStrandsMs.restype = C.c_int
     L.seeqdevScanPacked.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(seeqdev_packed_t), C.c_int, C.c_int]
     L.seeqdevScanPacked.restype = C.c_int
     L.seeqdevPackReads.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]

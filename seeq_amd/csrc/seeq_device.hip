@@ -22,7 +22,7 @@
  *
  * Here: plumbing, pattern handle, scan context, the segment and packed drivers, the scan
  * entries.  The side entries are included where they belong in that order: seeq_synth.h,
- * seeq_text_alloc.h, seeq_multi_host.h, seeq_demux_host.h, seeq_string.h.
+ * seeq_text_alloc.h, seeq_multi_host.h, seeq_demux_host.h, seeq_strand_host.h, seeq_string.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -106,6 +106,7 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_multi.h"
 #include "seeq_demux.h"
 #include "seeq_fastq.h"
+#include "seeq_strand.h"
 static_assert(sizeof(seeqdev_demux_t) == 16 && sizeof(seeqdev_hit_t) == sizeof(uint4), "demux records are written as uint4");
 #include "seeq_post.h"
 static_assert(STREAM_NW == STREAM_NW_HOST, "waves per k_stream workgroup");
@@ -147,6 +148,7 @@ struct seeqdev_pattern {
    int       quad_parts, quad_mp;
    double    quad_pacc;
    pthread_mutex_t plan_lock;   /* the automata are built on first use; scan contexts on several threads may share a pattern */
+   struct seeqdev_pattern *twin;   /* the reverse complement (seeq_strand_host.h): built by the first both-strands scan, owned */
 };
 
 /* FN<W>(...) for the W that holds a pattern of `words` Peq words: the five instances of the kernels templated on it (k_forward, k_exact, k_string) */
@@ -202,6 +204,7 @@ extern "C" int seeqdevPatternDevice(const seeqdev_pattern_t *p) { return p ? p->
 extern "C" void seeqdevPatternFree(seeqdev_pattern_t *p)
 {
    if (!p) return;
+   if (p->twin) seeqdevPatternFree(p->twin);
    (void)use_device(p->device);
    if (p->d_peq) (void)hipFree(p->d_peq);
    if (p->d_sdfa) (void)hipFree(p->d_sdfa);
@@ -491,6 +494,11 @@ struct seeqdev_scan {
    DemuxCnt *d_dmcnt, *h_dmcnt;                           /* h_ pinned */
    size_t    dm_nrec;                                     /* records of the last demux */
    uint64_t  dm_nlines;                                   /* its counted lines */
+   /* seeqdevScanRunStrands (seeq_strand.h): allocated by the first both-strands call */
+   seeqdev_hit_t *st_side; uint64_t *st_side_off; size_t cap_st_side;      /* two scans: the plus records and offsets, aside while the twin is scanned */
+   uint4    *st_mrg; uint64_t *st_mrg_off; uint32_t *st_bsum; size_t cap_st_mrg;      /* the merged records and offsets, the reduction's per-tile sums */
+   StrandCnt *d_stcnt, *h_stcnt;                          /* h_ pinned */
+   hipEvent_t ev_st[2]; bool have_st_ev; float st_merge_ms;      /* profiling: around the merge's launches and copies (the FASTQ filter not included) */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -610,6 +618,7 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
    if (!s) return;
    (void)use_device(s->device);
    if (s->have_h2d_ev) { (void)hipEventDestroy(s->ev_h2d[0]); (void)hipEventDestroy(s->ev_h2d[1]); }
+   if (s->have_st_ev) { (void)hipEventDestroy(s->ev_st[0]); (void)hipEventDestroy(s->ev_st[1]); }
    (void)hipStreamSynchronize(s->stream);
    ws_free_all(&s->ws);
    multi_plan_free(s->mplan);
@@ -1710,6 +1719,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 
 #include "seeq_multi_host.h"
 #include "seeq_demux_host.h"
+#include "seeq_strand_host.h"
 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {

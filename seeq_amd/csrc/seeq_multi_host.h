@@ -166,9 +166,10 @@ static void multi_gather_end(seeqdev_scan_t *s, int npat) { s->multi_first[npat]
 static int demux_one_walk(seeqdev_scan_t *s, int npat, uint64_t capR);
 
 /* 0: done; 1: not for this set / text / options (the caller scans pattern by pattern); -1: error.  demux: the records stay on
-   the device and are demultiplexed there (seeqdevScanRunDemux) instead of going to the host. */
+   the device and are demultiplexed there (seeqdevScanRunDemux) instead of going to the host.  stay: the records stay on the device,
+   in their regions of the record workspace, and that is all (seeqdevScanRunStrands merges them there). */
 static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pats, int npat, const void *d_text, size_t nbytes,
-                          int options, int want, seeqdev_counts_t *counts, bool demux = false)
+                          int options, int want, seeqdev_counts_t *counts, bool demux = false, bool stay = false)
 {
    const char *env = getenv("SEEQ_MULTI");
    if (env && !strcmp(env, "sequential")) return 1;
@@ -212,6 +213,7 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
             if (rc == 0) s->last_multi = 1;
             break;
          }
+         if (stay) { rc = 0; s->last_multi = 1; break; }
          s->multi_nrec = 0;
          rc = 0;
          if (want == SEEQDEV_WANT_RECORDS) {

@@ -107,6 +107,29 @@ def plain_pattern(pattern):
     return ''.join(out)
 
 
+_COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A", "U": "A", "N": "N", "a": "t", "c": "g", "g": "c", "t": "a", "u": "a", "n": "n"}
+
+
+def revcomp_pattern(pattern):
+    """The reverse complement of a pattern EXPRESSION: the tokens (a base, N, or a bracket class) in reverse order, every base
+    complemented -- a class member by member, so [AC] becomes [GT] and [] stays [].  U is read as T (its complement is A, and the
+    complement of A is written T); N stays N; case is preserved.  Compiles to the key bytes seeqdevPatternRevComp makes of the
+    compiled pattern."""
+    tokens, i = [], 0
+    try:
+        while i < len(pattern):
+            if pattern[i] == "[":
+                j = pattern.index("]", i)
+                tokens.append("[" + "".join(_COMPLEMENT[c] for c in pattern[i + 1:j]) + "]")
+                i = j + 1
+            else:
+                tokens.append(_COMPLEMENT[pattern[i]])
+                i += 1
+    except (KeyError, ValueError):
+        raise ValueError("not a pattern expression: %r" % (pattern,))
+    return "".join(reversed(tokens))
+
+
 class Pattern:
     def __init__(self, pattern, tau):
         self._lib = _capi.lib()
@@ -121,6 +144,34 @@ class Pattern:
         sq, self._sq = self._sq, None
         if sq:
             self._lib.seeqFree(sq)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def revcomp(self):
+        """The reverse complement as a pattern of its own (seeqdevPatternRevComp: same device, same tau), usable wherever a Pattern
+        is -- a barcode set with both orientations of every member, for one."""
+        return RevCompPattern(self)
+
+
+class RevCompPattern:
+    """What Pattern.revcomp() returns: `handle`, `pattern` (the expression, revcomp_pattern of the original's), `tau`, `wlen`;
+    close() frees it.  It does not depend on the Pattern it was made from."""
+
+    def __init__(self, of):
+        self._lib = _capi.lib()
+        self.pattern, self.tau, self.wlen = revcomp_pattern(of.pattern), of.tau, of.wlen
+        self.handle = self._lib.seeqdevPatternRevComp(of.handle)
+        if not self.handle:
+            raise SeeqDeviceError("seeqdevPatternRevComp(%r): %s" % (of.pattern, _capi.error_text()))
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h:
+            self._lib.seeqdevPatternFree(h)
 
     def __del__(self):
         try:
@@ -244,6 +295,46 @@ class Scanner:
         return res
 
 
+    # ---- both strands in one call (include/seeq_amd.h: seeqdevScanRunStrands / seeqdevScanHostStrands) ----
+    def _strands(self, call, want, copy):
+        cnt = _capi.seeqdev_counts_t()
+        per = (C.c_uint64 * 2)()
+        _check(call(C.byref(cnt), per))
+        res = dict(nlines=cnt.nlines, nmatchlines=cnt.nmatchlines, nhits=cnt.nhits, nrecords=cnt.nrecords, nheaders=cnt.nheaders,
+                   per_strand=[int(per[0]), int(per[1])])
+        if want == WANT_RECORDS and copy:
+            res["records"] = self.strand_records(cnt.nrecords)
+        return res
+
+    def strand_records(self, n, first=0):
+        """Copy records [first, first + n) of the last both-strands scan to the host -> structured array of STRAND_DTYPE: `dist`
+        without the strand bit, `strand` 0 (the pattern as given) or 1 (its reverse complement)."""
+        raw = self.records(n, first)
+        out = np.zeros(n, dtype=STRAND_DTYPE)
+        out["line"], out["start"], out["end"] = raw[:, 0], raw[:, 1], raw[:, 2]
+        out["dist"] = raw[:, 3] & np.uint32(~_capi.SEEQDEV_HIT_MINUS & 0xFFFFFFFF)
+        out["strand"] = raw[:, 3] >> np.uint32(31)
+        return out
+
+    def last_strands_merge_ms(self):
+        """Device time of the last both-strands call's merge (its kernels and device copies; profiling on), 0 when not measured."""
+        ms = C.c_float(0)
+        _check(self._lib.seeqdevScanLastStrandsMs(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def strands_host(self, pattern, data, options=0, want=WANT_RECORDS):
+        """data: bytes, staged once.  The text searched with `pattern` and with its reverse complement, the two record sets merged on
+        the device (seeq_amd.h: SQ_ALL every record of both in (line, end, strand) order; SQ_BEST / SQ_FIRST the winner of every line)
+        -> the counts dict plus per_strand [plus, minus] and, with WANT_RECORDS, records (STRAND_DTYPE); record_offsets() serves the
+        merged records' line offsets.  options may hold SEEQDEV_FASTA or SEEQDEV_FASTQ."""
+        return self._strands(lambda cnt, per: self._lib.seeqdevScanHostStrands(self._h, pattern.handle, data, len(data), options, want, cnt, per), want, True)
+
+    def strands_tensor(self, pattern, t, options=0, want=WANT_RECORDS, copy=True):
+        """t: torch uint8 CUDA tensor (contiguous), resident.  As strands_host; copy=False leaves the records on the device
+        (records_device_ptr / strand_records / records: seeqdev_hit_t with SEEQDEV_HIT_MINUS in dist)."""
+        return self._strands(lambda cnt, per: self._lib.seeqdevScanRunStrands(self._h, pattern.handle, C.c_void_p(t.data_ptr()), t.numel(), options, want,
+                                                                             cnt, per), want, copy)
+
     # ---- several patterns, one text (include/seeq_amd.h: seeqdevScanRunMulti / seeqdevScanHostMulti) ----
     def _multi(self, patterns, call, want, copy=True):
         n = len(patterns)
@@ -319,6 +410,9 @@ class Scanner:
         return self._demux(patterns, lambda arr, n, cnt, per: self._lib.seeqdevScanRunDemux(self._h, arr, n, C.c_void_p(t.data_ptr()), t.numel(),
                                                                                          options, cnt, per), copy)
 
+
+# One record of seeqdevScanRunStrands as strand_records() returns it: the 16-byte seeqdev_hit_t with the strand bit of `dist` taken out.
+STRAND_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("dist", "<u4"), ("strand", "u1")])
 
 # One record of seeqdevScanRunDemux (seeq_amd.h: seeqdev_demux_t, 16 bytes).
 DEMUX_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("dist", "<u2"), ("pattern", "u1"), ("margin", "u1")])
