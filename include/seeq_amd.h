@@ -140,6 +140,13 @@ int seeqdevScanLastFilter(const seeqdev_scan_t * scan);
 /* 1 when the last packed run (path 8) walked the pattern's QUAD table -- four bases, one packed byte, per table step over a small
  * partition-filter automaton (seeq_dfa.h section 3b) -- instead of the pair table (two bases per step). */
 int seeqdevScanLastPackedQuad(const seeqdev_scan_t * scan);
+/* The runs the last completed scan took: 1 = the first run's counters were the result, more = the device reported a workspace too
+ * small or a kernel that could not serve the text, and the scan was run again (seeqdevScanFetch).  Of a multi-pattern, demux or
+ * both-strands call: the runs of its last scan or walk.  0 before the first scan. */
+int seeqdevScanLastRuns(const seeqdev_scan_t * scan);
+/* The fall-back flags the context remembers of earlier texts (a long line among reads, foreign bytes, a line across a segment
+ * seam ...: internal bits, 0 = none) and the scans they stay in force for; either pointer may be NULL.  Read-only. */
+int seeqdevScanFallback(const seeqdev_scan_t * scan, unsigned * bits, int * scans_left);
 
 /* Enqueue (asynchronously, on the context's stream) the whole hot path over
  * d_text[0..nbytes): newline index -> per-line forward scan -> hit-line

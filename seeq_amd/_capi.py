@@ -85,6 +85,7 @@ EXPORTS = [
     "seeqdevScanRunMulti", "seeqdevScanHostMulti", "seeqdevScanMultiRecords", "seeqdevScanLastMulti", "seeqdevScanPacked", "seeqdevPackReads", "seeqdevPackReadsDevice",
     "seeqdevScanRunDemux", "seeqdevScanHostDemux", "seeqdevScanDemuxDevice", "seeqdevScanCopyDemux",
     "seeqdevPatternRevComp", "seeqdevScanRunStrands", "seeqdevScanHostStrands", "seeqdevScanLastStrandsMs",
+    "seeqdevScanLastRuns", "seeqdevScanFallback",
 ]
 
 
@@ -198,6 +199,10 @@ def lib():
     L.seeqdevScanLastFilter.restype = C.c_int
     L.seeqdevScanLastPackedQuad.argtypes = [C.c_void_p]
     L.seeqdevScanLastPackedQuad.restype = C.c_int
+    L.seeqdevScanLastRuns.argtypes = [C.c_void_p]
+    L.seeqdevScanLastRuns.restype = C.c_int
+    L.seeqdevScanFallback.argtypes = [C.c_void_p, P(C.c_uint), P(C.c_int)]
+    L.seeqdevScanFallback.restype = C.c_int
     L.seeqdevScanRunMulti.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
     L.seeqdevScanRunMulti.restype = C.c_int
     L.seeqdevScanHostMulti.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]

@@ -508,6 +508,7 @@ struct seeqdev_scan {
    /* last run (for the transparent re-run on overflow) */
    const seeqdev_pattern *pat; const void *text; size_t nbytes; int options, want;
    bool ran;
+   int  last_runs;             /* runs the last completed scan (or one walk) took: 1 = no re-run */
    seeqdev_counts_t counts;
    /* profiling */
    bool prof;
@@ -708,6 +709,15 @@ extern "C" int seeqdevScanSetLineHint(seeqdev_scan_t *s, double avg_bytes_per_li
 extern "C" int seeqdevScanLastPath(const seeqdev_scan_t *s) { return s ? s->last_path : 0; }
 extern "C" int seeqdevScanLastFilter(const seeqdev_scan_t *s) { return s && s->last_filter ? 1 : 0; }
 extern "C" int seeqdevScanLastPackedQuad(const seeqdev_scan_t *s) { return s && s->last_packed_quad ? 1 : 0; }
+extern "C" int seeqdevScanLastRuns(const seeqdev_scan_t *s) { return s ? s->last_runs : 0; }
+
+extern "C" int seeqdevScanFallback(const seeqdev_scan_t *s, unsigned *bits, int *scans_left)
+{
+   if (!s) { errno = EINVAL; return -1; }
+   if (bits) *bits = s->fallback.bits;
+   if (scans_left) *scans_left = s->fallback.bits ? s->fallback.ttl : 0;
+   return 0;
+}
 
 extern "C" int seeqdevScanSetProfiling(seeqdev_scan_t *s, int on)
 {
@@ -1513,6 +1523,7 @@ extern "C" int seeqdevScanFetch(seeqdev_scan_t *s, seeqdev_counts_t *counts)
       const int next = rerun_next(s, run, h);
       if (next < 0) return -1;
       if (next == 0) {
+         s->last_runs = run + 1;
          if (s->fastq) {
             if (!s->fq_done && fastq_finish(s, h)) return -1;
             s->fq_done = true;

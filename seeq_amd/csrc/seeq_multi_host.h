@@ -204,7 +204,8 @@ static int multi_one_pass(seeqdev_scan_t *s, const seeqdev_pattern_t *const *pat
           hipStreamSynchronize(s->stream) != hipSuccess) { errno = EIO; break; }
       const int next = rerun_next(s, run, *s->h_cnt, s->h_mcnt, npat);
       if (next == 1) continue;
-      if (next == 2) rc = 1;                                /* not k_pair's text after all: a scan per pattern */
+      s->last_runs = run + 1;
+      if (next == 2) rc = 1;                               /* not k_pair's text after all: a scan per pattern */
       if (next == 0) {
          /* results: counts, then every pattern's records from its region */
          const uint64_t capR = s->cap_records / (uint64_t)npat;

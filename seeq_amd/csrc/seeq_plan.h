@@ -139,7 +139,11 @@ static inline ScanPlan seeq_plan_scan(const PlanIn &in, PlanAutomata &au, seeq_p
       partition filter, so every hit line of it is a candidate.  Read-length lines under SQ_FAIL / SQ_CONVERT (aliased bytes
       keep a superset a superset; a skipped byte, SQ_IGNORE, does not), while it makes few false candidates. */
    {
-      const bool long_lines = (in.avg_line > 600.0 && kn.kernel != 3) || in.force_ll;      /* (a candidate inside a line of a whole tile sets force_ll) */
+      /* (a candidate inside a line of a whole tile sets force_ll.  Not for several patterns in one walk: the flag is what a single-pattern scan of an
+         EARLIER text left, the walk has no long-line variant to go to and notices such a line itself -- RERUN_NOT_ONE_WALK --, so it is tried on
+         every text whose sample looks read-length; with the flag in its way a context that met one long line scanned the next 32 barcode sets
+         pattern by pattern) */
+      const bool long_lines = (in.avg_line > 600.0 && kn.kernel != 3) || (in.force_ll && !in.multi_active);
       /* (round 5: long lines too -- LL in seeq_pair.h -- under SQ_FAIL / SQ_CONVERT on plain text, for one pattern, while its automaton flags few enough
          positions for the window walk: the rule of k_stream's long-line filters below, with the restart walk's cost per candidate) */
       const bool pair_ll = long_lines && (nd == 0 || nd == PLAN_SQ_CONVERT) && !fasta && !in.multi_active && kn.kernel != 1 && !kn.no_window;

@@ -224,6 +224,17 @@ class Scanner:
         """True when the last packed run walked the quad table (four bases per table step)."""
         return bool(self._lib.seeqdevScanLastPackedQuad(self._h))
 
+    def last_runs(self):
+        """Runs the last completed scan took (1: no re-run; of a multi, demux or both-strands call: those of its last scan or walk)."""
+        return int(self._lib.seeqdevScanLastRuns(self._h))
+
+    def fallback(self):
+        """(bits, scans_left): the fall-back flags the context remembers of earlier texts (FALLBACK_* below; 0: none) and the scans
+        they stay in force for."""
+        bits, left = C.c_uint(0), C.c_int(0)
+        _check(self._lib.seeqdevScanFallback(self._h, C.byref(bits), C.byref(left)))
+        return int(bits.value), int(left.value)
+
     def last_times_ms(self):
         ms = (C.c_float * 4)()
         _check(self._lib.seeqdevScanLastTimes(self._h, ms))
@@ -410,6 +421,9 @@ class Scanner:
         return self._demux(patterns, lambda arr, n, cnt, per: self._lib.seeqdevScanRunDemux(self._h, arr, n, C.c_void_p(t.data_ptr()), t.numel(),
                                                                                          options, cnt, per), copy)
 
+
+# Scanner.fallback(): the bits (csrc/seeq_types.h, OVF_*) that set a context's fall-back flags
+FALLBACK_NO_STREAM, FALLBACK_NONDNA, FALLBACK_LONG_LINES, FALLBACK_SEAM, FALLBACK_LEADER = 8, 16, 32, 128, 256
 
 # One record of seeqdevScanRunStrands as strand_records() returns it: the 16-byte seeqdev_hit_t with the strand bit of `dist` taken out.
 STRAND_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("dist", "<u4"), ("strand", "u1")])

@@ -75,6 +75,16 @@ def test_no_gpu_fails_loudly(capi):
         seeq_amd.compile("ACGT", 1)
 
 
+def test_context_state_getters_without_a_context(capi):
+    """seeqdevScanLastRuns / seeqdevScanFallback read host fields only: no context, no runs and EINVAL -- the outputs untouched."""
+    L = capi.lib()
+    assert L.seeqdevScanLastRuns(None) == 0
+    bits, left = C.c_uint(7), C.c_int(7)
+    C.set_errno(0)
+    assert L.seeqdevScanFallback(None, C.byref(bits), C.byref(left)) == -1
+    assert C.get_errno() == errno.EINVAL and (bits.value, left.value) == (7, 7)
+
+
 def test_seeqopen_errors(capi):
     L = capi.lib()
     assert not L.seeqOpen(b"/nonexistent/invented.txt")

@@ -114,6 +114,30 @@ def _check(sc, res, exp, offsets, records=True):
     assert sc.record_offsets(len(got)).tolist() == [offsets[r[0]] for r in exp.rows]
 
 
+# ---- one step: the call, its check, and on failure the same call on a fresh Scanner ----
+def _step(sc, what, call, check, fresh=None):
+    """check(scanner, call(scanner)) on the long-lived context; when that fails, once more on a fresh Scanner (made by `fresh`, in the
+    same environment), and the message says which of the two it is."""
+    from seeq_amd import device as dev
+    try:
+        check(sc, call(sc))
+        return
+    except (AssertionError, dev.SeeqDeviceError) as e:
+        first = e
+    text = str(first).lower()
+    if isinstance(first, dev.SeeqDeviceError) and ("illegal" in text or "launch failure" in text or "hardware" in text):
+        raise first                                        # a device fault: nothing more is started on it
+    other = (fresh or dev.Scanner)()
+    try:
+        check(other, call(other))
+        verdict = "the same call on a fresh Scanner PASSES: a state bug of the long-lived context"
+    except (AssertionError, dev.SeeqDeviceError) as e:
+        verdict = "the same call on a fresh Scanner FAILS too (%s): a kernel bug" % (str(e).splitlines() or [""])[0][:200]
+    finally:
+        other.close()
+    raise AssertionError("%s: %s: %s\n-- %s" % (what, type(first).__name__, first, verdict)) from first
+
+
 @pytest.fixture(scope="module")
 def texts():
     """Per pattern: its lines' buffer and line offsets, made once."""
@@ -382,3 +406,194 @@ def test_demux_in_both_orientations(gpu, capi, oracle):
     sc.close()
     for p in ps:
         p.close()
+
+
+# ---- both strands under pressure: small segments, a tiny workspace, a one walk that gives up, shrinking and growing calls ----
+SEG = 65536
+TILE = 8192                    # bytes of a k_pair tile: a candidate in a tile without a newline is long-line input
+
+
+def _fastq_text(seqs, expr, seed):
+    """Four-line records around the sequence lines (headers that carry the pattern, quality lines of A / C / G) -> (buffer, buffer of
+    the sequence lines alone, offsets: record r -> its sequence line in the buffer)."""
+    rng = random.Random(seed)
+    raw = []
+    for i, sq in enumerate(seqs):
+        raw += ["@read%d %s" % (i, expr), sq, "+", "".join(rng.choice("ACG") for _ in sq)]
+    buf = _buf(raw)
+    raw_offsets = _line_offsets(buf)
+    return buf, _buf(seqs), [None] + [raw_offsets[4 * r + 2] for r in range(len(seqs))]
+
+
+def _segments_with_both_strands(exp, offsets):
+    return len({offsets[r[0]] // SEG for r in exp.plus} & {offsets[r[0]] // SEG for r in exp.minus})
+
+
+@pytest.mark.parametrize("mode", sorted(MODES))
+@pytest.mark.parametrize("name", ["barcode", "classy", "pat20"])
+def test_strands_over_small_segments(gpu, capi, texts, expected, pats, name, mode, monkeypatch):
+    """Segments of 64 KiB: more than six of them, records of both strands in at least three; the one walk's regions and the side
+    arrays of the two scans are filled segment by segment."""
+    from seeq_amd import device as dev
+    monkeypatch.setenv("SEEQ_SEGMENT_BYTES", str(SEG))
+    buf, offsets = texts[name]
+    assert len(buf) > 6 * SEG and _segments_with_both_strands(expected(name, SQ_ALL), offsets) >= 3
+    sc = dev.Scanner()
+
+    def check(s, res):
+        _check(s, res, expected(name, MODES[mode]), offsets)
+        assert s.last_multi_one_pass() == (name != "pat20")      # (the class pattern is barcode-sized too: 10 positions, distance 1)
+    _step(sc, "%s, mode %s, 64 KiB segments" % (name, mode), lambda s: s.strands_host(pats[name], buf, MODES[mode], dev.WANT_RECORDS), check)
+    sc.close()
+
+
+def test_strands_fastq_over_small_segments(gpu, capi, oracle, monkeypatch):
+    from seeq_amd import device as dev
+    monkeypatch.setenv("SEEQ_SEGMENT_BYTES", str(SEG))
+    expr, tau = CASES["barcode"]
+    buf, seq_buf, offsets = _fastq_text(_lines(expr, tau, 2400, 31, lengths=(75, 100, 101)), expr, 32)
+    p = dev.Pattern(expr, tau)
+    sc = dev.Scanner()
+    for mode in (SQ_ALL, SQ_BEST):
+        exp = Expected(oracle, expr, tau, seq_buf, mode)
+        assert len(buf) > 6 * SEG and _segments_with_both_strands(exp, offsets) >= 3
+        _step(sc, "FASTQ, mode %d, 64 KiB segments" % mode, lambda s: s.strands_host(p, buf, mode | dev.SEEQDEV_FASTQ, dev.WANT_RECORDS),
+              lambda s, res: _check(s, res, exp, offsets))
+        assert sc.last_multi_one_pass()
+    sc.close()
+    p.close()
+
+
+@pytest.fixture(scope="module")
+def skewed():
+    """Barcode lines with three minus plants for every plus one: in a call of two scans the twin's scan, too, outgrows the workspace
+    that the scan before it left."""
+    expr, tau = CASES["barcode"]
+    lines = _lines(expr, tau, 3000, 23, strand_of=lambda i: 0 if i % 4 == 0 else 1)
+    return lines, _buf(lines)
+
+
+def _tiny():
+    from seeq_amd import device as dev
+    sc = dev.Scanner()
+    sc.reserve(0, 10, 2, 1)                                # every capacity overflows, and the optimistic first reservation is off for good
+    return sc
+
+
+@pytest.mark.parametrize("what", ["all", "best", "countmatch"])
+@pytest.mark.parametrize("path", ["one_walk", "sequential"])
+def test_strands_in_a_tiny_workspace(gpu, capi, oracle, pats, skewed, path, what, monkeypatch):
+    from seeq_amd import device as dev
+    if path == "sequential":
+        monkeypatch.setenv("SEEQ_MULTI", "sequential")
+    expr, tau = CASES["barcode"]
+    lines, buf = skewed
+    offsets = _line_offsets(buf)
+    mode, want = {"all": (SQ_ALL, dev.WANT_RECORDS), "best": (SQ_BEST, dev.WANT_RECORDS), "countmatch": (0, dev.WANT_COUNTMATCH)}[what]
+    exp = Expected(oracle, expr, tau, buf, SQ_ALL if what == "countmatch" else mode)
+    assert len(exp.minus) > 1.5 * len(exp.plus) + 64 and len(exp.plus) > 256      # (a re-run leaves an eighth to spare: the twin needs more)
+    sc = _tiny()
+    for i in range(2):                                     # (the second call: in the workspace the first one grew)
+        _step(sc, "tiny workspace, %s, %s, call %d" % (path, what, i), lambda s: s.strands_host(pats["barcode"], buf, mode, want),
+              lambda s, res: _check(s, res, exp, offsets, records=want == dev.WANT_RECORDS), fresh=_tiny)
+        assert sc.last_multi_one_pass() == (path == "one_walk")
+        if i == 0:
+            print(path, what, "runs of the last scan or walk:", sc.last_runs())
+            assert sc.last_runs() > 1
+    sc.close()
+
+
+@pytest.mark.parametrize("path", ["one_walk", "sequential"])
+def test_strands_fastq_in_a_tiny_workspace(gpu, capi, oracle, pats, skewed, path, monkeypatch):
+    """The filter's scratch follows the record arrays that the scans and strands_merge grow (cap_fq == cap_records)."""
+    from seeq_amd import device as dev
+    if path == "sequential":
+        monkeypatch.setenv("SEEQ_MULTI", "sequential")
+    expr, tau = CASES["barcode"]
+    buf, seq_buf, offsets = _fastq_text(skewed[0], expr, 33)
+    sc = _tiny()
+    for i, mode in enumerate((SQ_ALL, SQ_BEST, SQ_ALL)):
+        exp = Expected(oracle, expr, tau, seq_buf, mode)
+        assert len(exp.minus) > 1.5 * len(exp.plus) + 64 and len(exp.plus) > 256
+        _step(sc, "tiny workspace, FASTQ, %s, mode %d" % (path, mode), lambda s: s.strands_host(pats["barcode"], buf, mode | dev.SEEQDEV_FASTQ, dev.WANT_RECORDS),
+              lambda s, res: _check(s, res, exp, offsets), fresh=_tiny)
+        assert sc.last_multi_one_pass() == (path == "one_walk")
+        if i == 0:
+            assert sc.last_runs() > 1
+    # and unflagged afterwards: the scratch stays behind the record arrays
+    plain = Expected(oracle, expr, tau, buf, SQ_ALL)
+    _step(sc, "tiny workspace, after FASTQ, %s" % path, lambda s: s.strands_host(pats["barcode"], buf, SQ_ALL, dev.WANT_RECORDS),
+          lambda s, res: _check(s, res, plain, _line_offsets(buf)), fresh=_tiny)
+    sc.close()
+
+
+def test_strands_one_walk_that_gives_up(gpu, capi, oracle, texts, expected, pats):
+    """Reads with one line of four tiles that has hits on both strands: the sample says read-length lines and the context has no
+    fall-back flag, so the pair is walked once -- as the clean text before it is -- until the device meets the long line
+    (RERUN_NOT_ONE_WALK); two scans finish the call.  The next call on the clean text is one walk again."""
+    from seeq_amd import device as dev
+    expr, tau = CASES["barcode"]
+    plain = [dev.plain_pattern(expr), dev.plain_pattern(dev.revcomp_pattern(expr))]
+    rng = random.Random(34)
+    big = [rng.choice("ACGT") for _ in range(4 * TILE)]
+    for j in range(40):
+        c = _mutate(rng, plain[j % 2], rng.randint(0, tau))
+        q = rng.randrange(len(big) - len(c))
+        big[q:q + len(c)] = list(c)
+    lines = _lines(expr, tau, 3000, 35)
+    lines.insert(2000, "".join(big)[:4 * TILE])
+    buf = _buf(lines)
+    assert sum(len(ln) + 1 for ln in lines[:2000]) > 2 * SEG           # (the sample, 64 KiB, holds reads only)
+    offsets = _line_offsets(buf)
+    clean, clean_offsets = texts["barcode"]
+    sc = dev.Scanner()
+
+    def one_walk(s, res):
+        _check(s, res, expected("barcode", SQ_ALL), clean_offsets)
+        assert s.last_multi_one_pass()
+    _step(sc, "the clean text first", lambda s: s.strands_host(pats["barcode"], clean, SQ_ALL, dev.WANT_RECORDS), one_walk)
+    assert sc.fallback() == (0, 0)
+    for mode in (SQ_ALL, SQ_BEST):
+        exp = Expected(oracle, expr, tau, buf, mode)
+        if mode == SQ_ALL:
+            assert sum(1 for r in exp.plus if r[0] == 2001) >= 5 and sum(1 for r in exp.minus if r[0] == 2001) >= 5
+
+        def gave_up(s, res):
+            _check(s, res, exp, offsets)
+            assert not s.last_multi_one_pass()
+            assert s.fallback()[0] & dev.FALLBACK_LONG_LINES       # met on the device, not planned for
+        _step(sc, "reads around a long line, mode %d" % mode, lambda s: s.strands_host(pats["barcode"], buf, mode, dev.WANT_RECORDS), gave_up)
+    _step(sc, "the clean text after it", lambda s: s.strands_host(pats["barcode"], clean, SQ_ALL, dev.WANT_RECORDS), one_walk)
+    sc.close()
+
+
+@pytest.mark.parametrize("name,expr,tau", [("barcode", "ACGTTGCA", 1), ("pat20", PAT20, 1)])
+def test_strands_shrinking_and_growing(gpu, capi, oracle, name, expr, tau):
+    """One context: 20 lines, the full text, 20 lines again, a text without a minus record, the full text -- under SQ_ALL, SQ_BEST and with
+    SEEQDEV_FASTQ: the side arrays, the merged arrays and the one walk's regions hold the records of the larger call before beyond n."""
+    from seeq_amd import device as dev
+    if name == "pat20":
+        seqs = {"small": _lines(expr, tau, 20, 36, strand_of=lambda i: 0), "full": _lines(expr, tau, 3000, 37),
+                "plus_only": _lines(expr, tau, 3000, 38, strand_of=lambda i: 0)}
+    else:
+        # (random text holds the 8-mer's twin within one error now and then: lines of A and G around exact copies hold none)
+        rng = random.Random(36)
+        purine = ["".join(rng.choice("AG") for _ in range(40)) + (expr if i % 2 else "") + "".join(rng.choice("AG") for _ in range(40)) for i in range(400)]
+        seqs = {"small": purine[:20], "full": _lines(expr, tau, 3000, 37), "plus_only": purine}
+    p = dev.Pattern(expr, tau)
+    sc = dev.Scanner()
+    for mode, fastq in ((SQ_ALL, False), (SQ_BEST, False), (SQ_ALL, True)):
+        made = {}
+        for k, ls in seqs.items():
+            buf, seq_buf, offsets = _fastq_text(ls, expr, 39) if fastq else (_buf(ls), _buf(ls), _line_offsets(_buf(ls)))
+            made[k] = (buf, Expected(oracle, expr, tau, seq_buf, mode), offsets)
+        assert len(made["full"][1].minus) > 1024 and len(made["full"][1].plus) > 1024
+        assert len(made["plus_only"][1].minus) == 0 and len(made["small"][1].minus) == 0 and len(made["small"][1].plus) > 0
+        for k in ("small", "full", "small", "plus_only", "full", "plus_only"):
+            buf, exp, offsets = made[k]
+            _step(sc, "%s, mode %d%s, the %s text" % (name, mode, ", FASTQ" if fastq else "", k),
+                  lambda s: s.strands_host(p, buf, mode | (dev.SEEQDEV_FASTQ if fastq else 0), dev.WANT_RECORDS), lambda s, res: _check(s, res, exp, offsets))
+            if k == "full":
+                assert sc.last_multi_one_pass() == (name == "barcode")
+    sc.close()
+    p.close()

@@ -794,6 +794,10 @@ def test_scan_plans_of_the_baseline_configurations(harness):
     assert (p["path"], p["use_pair"], p["stream_ll"], p["window_ok"], p["order2"]) == (6, 1, 1, 0, 0), p
     p = plan(head, 3, SQ_BEST | SQ_IGNORE, RECORDS, 151.0, flags=1)
     assert (p["use_pair"], p["stream_ll"]) == (0, 1) or p["path"] in (1, 3), p
+    # ... but several patterns in one walk are not kept off k_pair by it: the walk notices a long line itself and gives up (RERUN_NOT_ONE_WALK)
+    p = plan(head[:10], 1, SQ_BEST, RECORDS, 151.0, flags=1 | 32)
+    assert (p["rc"], p["path"], p["use_pair"], p["stream_ll"], p["window_ok"]) == (0, 6, 1, 0, 1), p
+    assert plan(head[:10], 1, SQ_BEST, RECORDS, 1.3e8, flags=32)["rc"] == -2      # (a sample of long lines: a scan per pattern, as before)
 
 
 def test_workspace_growth_is_grouped_and_every_refusal_leaves_it_whole(harness):
