@@ -307,6 +307,68 @@ int seeqdevScanHostStrands(seeqdev_scan_t * scan, const seeqdev_pattern_t * pat,
  * (profiling on; 0 otherwise, and when there was nothing to merge). */
 int seeqdevScanLastStrandsMs(const seeqdev_scan_t * scan, float * merge_ms);
 
+/* THE INSERT BETWEEN TWO FLANKS.  What a constant sequence is most often searched for in reads: to cut out what lies next to it -- a
+ * barcode, a guide, a UMI between two constant flanks (the reference's Python module ships the one-string form as matchPrefix /
+ * matchSuffix).  seeqdevScanRunInserts / seeqdevScanHostInserts: the text is scanned with `right` under SQ_ALL (every occurrence; its
+ * records and offsets are copied aside on the device) and with `left` under the call's match mode (SQ_BEST, what matchPrefix / matchSuffix
+ * use, or SQ_FIRST: one record per matching line), each scan bit-exact with the reference as every scan here is, and the two record sets
+ * are joined line by line ON THE DEVICE (seeq_insert.h):
+ *   admissible           a right record R of the line of a left record L with R.start >= L.end + min_len and, when max_len != 0,
+ *                        R.start <= L.end + max_len (sums in 64 bits; max_len == 0: no upper bound);
+ *   chosen               SQ_BEST: the admissible record of smallest dist, the smaller end on a tie; SQ_FIRST: the one of smallest end;
+ *   result               one seeqdev_insert_t per line with a left record and a chosen right record, in ascending line order, and beside
+ *                        each its line's byte offset in the scanned buffer (as seeqdevScanCopyOffsets).  The insert is bytes
+ *                        [start, end) of the line; start == end is an empty insert.
+ * The two flanks are patterns of their own (length, distance); the same handle for both is legal.  Synchronous.  The result lives in
+ * arrays of its own -- seeqdevScanInsertsDevice / seeqdevScanCopyInserts / seeqdevScanCopyInsertOffsets -- and stays valid until the
+ * context's next inserts call or seeqdevScanFree.  Afterwards the context is as after a both-strands call: seeqdevScanFetch fails
+ * (EINVAL) until the next scan, the next plain scan answers as on a fresh context, seeqdevScanLastRuns gives the runs of the call's
+ * last scan (the left one).
+ * `options`: the match mode (SQ_BEST / SQ_FIRST), the non-DNA mode, SEEQDEV_FASTA, SEEQDEV_FASTQ -- the flags go to both scans unchanged,
+ * so under SEEQDEV_FASTQ only sequence lines have records, `line` is the record number and the offsets are those of the sequence lines in
+ * the original buffer.  EINVAL, before any device call: SQ_ALL or SQ_COUNT as the mode, SEEQDEV_SINGLELINE, an input-mode bit
+ * (SQ_STREAM), NULL scan / left / right / counts, NULL text with bytes, max_len != 0 && min_len > max_len, a pattern on another device,
+ * SEEQDEV_FASTA together with SEEQDEV_FASTQ.  E2BIG: more than 2^32 - 1 records in either list.
+ * ONE orientation per call: for reads off the other strand call again with left = seeqdevPatternRevComp(right) and
+ * right = seeqdevPatternRevComp(left).  One-sided cuts (what lies before a right flank alone, after a left flank alone) need line
+ * lengths, which the records do not carry: not served.
+ * seeqdevScanInsertText: the inserts cut out of the text, on the device -- every insert's bytes followed by '\n', in record order (output
+ * line k is record k; an empty insert is an empty line), ready for the next stage (a second scan, seeqdevScanRunDemux).  d_text / nbytes:
+ * the text the call scanned; d_text == NULL: the context's staged text of the last seeqdevScanHostInserts (EINVAL when another host call
+ * has staged over it since).  *out_bytes is always set to counts.text_bytes; out_cap < text_bytes: ERANGE, nothing is written;
+ * d_out == NULL with out_cap == 0: the size query.  A record that reaches beyond nbytes: EIO.  Synchronous.
+ * Device memory of its own (allocated by a context's first such call, freed with it): 24 bytes per right record kept aside (the
+ * both-strands call's side copy: one owner), 16 per left record, 32 per insert.  (The reference cuts one string per call: an addition
+ * of this boundary.) */
+typedef struct {
+   uint32_t line;    /* 1-based, numbered as seeqdev_hit_t.line */
+   uint32_t start;   /* = the left record's end: first byte of the insert within the line */
+   uint32_t end;     /* = the chosen right record's start, exclusive; start == end is an empty insert */
+   uint16_t ldist;   /* distance of the left flank's match */
+   uint16_t rdist;   /* distance of the right flank's */
+} seeqdev_insert_t;  /* 16 bytes */
+
+typedef struct {
+   uint64_t nlines;      /* counted lines, as seeqdev_counts_t.nlines */
+   uint64_t nleft;       /* lines with a left record */
+   uint64_t nright;      /* lines with at least one right record */
+   uint64_t nboth;       /* lines with both */
+   uint64_t ninserts;    /* records produced; nboth - ninserts: both flanks there, in the wrong order or the wrong distance apart */
+   uint64_t text_bytes;  /* sum over the records of end - start + 1: the size of the insert text */
+} seeqdev_insert_counts_t;
+
+int seeqdevScanRunInserts (seeqdev_scan_t * scan, const seeqdev_pattern_t * left, const seeqdev_pattern_t * right, const void * d_text,    size_t nbytes,
+                           int options, uint32_t min_len, uint32_t max_len, seeqdev_insert_counts_t * counts);
+int seeqdevScanHostInserts(seeqdev_scan_t * scan, const seeqdev_pattern_t * left, const seeqdev_pattern_t * right, const char * host_text, size_t nbytes,
+                           int options, uint32_t min_len, uint32_t max_len, seeqdev_insert_counts_t * counts);
+const seeqdev_insert_t * seeqdevScanInsertsDevice(const seeqdev_scan_t * scan);
+int seeqdevScanCopyInserts(seeqdev_scan_t * scan, seeqdev_insert_t * host_out, size_t first, size_t n);
+int seeqdevScanCopyInsertOffsets(seeqdev_scan_t * scan, uint64_t * host_out, size_t first, size_t n);
+int seeqdevScanInsertText(seeqdev_scan_t * scan, const void * d_text, size_t nbytes, void * d_out, size_t out_cap, uint64_t * out_bytes);
+/* Device time (ms) of the last inserts call's join -- its four launches, between two HIP events on the context's stream (profiling on; 0
+ * otherwise, and when there was nothing to join). */
+int seeqdevScanLastInsertsMs(const seeqdev_scan_t * scan, float * join_ms);
+
 /* PACKED READ BATCHES -- 2 bits per base instead of a byte: a quarter of the HBM (and PCIe) traffic of the ASCII scan for
  * read sets that are kept packed anyway (BAM, .2bit, a sequencer's own format).  Layout, all device pointers:
  *   bases : four bases per byte, the FIRST base of a byte in its bits 7-6; code = (ASCII >> 1) & 3, i.e. A 0, C 1, T/U 2, G 3;

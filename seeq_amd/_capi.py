@@ -68,6 +68,15 @@ class seeqdev_demux_counts_t(C.Structure):
     _fields_ = [("nlines", C.c_uint64), ("nassigned", C.c_uint64), ("nambiguous", C.c_uint64)]
 
 
+class seeqdev_insert_t(C.Structure):
+    _fields_ = [("line", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("ldist", C.c_uint16), ("rdist", C.c_uint16)]
+
+
+class seeqdev_insert_counts_t(C.Structure):
+    _fields_ = [("nlines", C.c_uint64), ("nleft", C.c_uint64), ("nright", C.c_uint64), ("nboth", C.c_uint64), ("ninserts", C.c_uint64),
+                ("text_bytes", C.c_uint64)]
+
+
 # Every symbol the three public headers declare (tests check the .so exports all of them).
 EXPORTS = [
     # libseeq.h
@@ -85,6 +94,8 @@ EXPORTS = [
     "seeqdevScanRunMulti", "seeqdevScanHostMulti", "seeqdevScanMultiRecords", "seeqdevScanLastMulti", "seeqdevScanPacked", "seeqdevPackReads", "seeqdevPackReadsDevice",
     "seeqdevScanRunDemux", "seeqdevScanHostDemux", "seeqdevScanDemuxDevice", "seeqdevScanCopyDemux",
     "seeqdevPatternRevComp", "seeqdevScanRunStrands", "seeqdevScanHostStrands", "seeqdevScanLastStrandsMs",
+    "seeqdevScanRunInserts", "seeqdevScanHostInserts", "seeqdevScanInsertsDevice", "seeqdevScanCopyInserts", "seeqdevScanCopyInsertOffsets",
+    "seeqdevScanInsertText", "seeqdevScanLastInsertsMs",
     "seeqdevScanLastRuns", "seeqdevScanFallback",
 ]
 
@@ -229,6 +240,22 @@ def lib():
     L.seeqdevScanHostStrands.restype = C.c_int
     L.seeqdevScanLastStrandsMs.argtypes = [C.c_void_p, P(C.c_float)]
     L.seeqdevScanLastStrandsMs.restype = C.c_int
+    L.seeqdevScanRunInserts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32,
+                                        P(seeqdev_insert_counts_t)]
+    L.seeqdevScanRunInserts.restype = C.c_int
+    L.seeqdevScanHostInserts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32,
+                                         P(seeqdev_insert_counts_t)]
+    L.seeqdevScanHostInserts.restype = C.c_int
+    L.seeqdevScanInsertsDevice.argtypes = [C.c_void_p]
+    L.seeqdevScanInsertsDevice.restype = C.c_void_p
+    L.seeqdevScanCopyInserts.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+    L.seeqdevScanCopyInserts.restype = C.c_int
+    L.seeqdevScanCopyInsertOffsets.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+    L.seeqdevScanCopyInsertOffsets.restype = C.c_int
+    L.seeqdevScanInsertText.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, P(C.c_uint64)]
+    L.seeqdevScanInsertText.restype = C.c_int
+    L.seeqdevScanLastInsertsMs.argtypes = [C.c_void_p, P(C.c_float)]
+    L.seeqdevScanLastInsertsMs.restype = C.c_int
     L.seeqdevScanPacked.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(seeqdev_packed_t), C.c_int, C.c_int]
     L.seeqdevScanPacked.restype = C.c_int
     L.seeqdevPackReads.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]

@@ -22,7 +22,8 @@
  *
  * Here: plumbing, pattern handle, scan context, the segment and packed drivers, the scan
  * entries.  The side entries are included where they belong in that order: seeq_synth.h,
- * seeq_text_alloc.h, seeq_multi_host.h, seeq_demux_host.h, seeq_strand_host.h, seeq_string.h.
+ * seeq_text_alloc.h, seeq_multi_host.h, seeq_demux_host.h, seeq_strand_host.h, seeq_insert_host.h,
+ * seeq_string.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -107,7 +108,9 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_demux.h"
 #include "seeq_fastq.h"
 #include "seeq_strand.h"
+#include "seeq_insert.h"
 static_assert(sizeof(seeqdev_demux_t) == 16 && sizeof(seeqdev_hit_t) == sizeof(uint4), "demux records are written as uint4");
+static_assert(sizeof(seeqdev_insert_t) == sizeof(uint4), "insert records are written as uint4");
 #include "seeq_post.h"
 static_assert(STREAM_NW == STREAM_NW_HOST, "waves per k_stream workgroup");
 extern "C" {
@@ -494,11 +497,21 @@ struct seeqdev_scan {
    DemuxCnt *d_dmcnt, *h_dmcnt;                           /* h_ pinned */
    size_t    dm_nrec;                                     /* records of the last demux */
    uint64_t  dm_nlines;                                   /* its counted lines */
+   /* the first scan's records and offsets of a call that scans twice, aside on the device while the second scan runs (side_keep, seeq_strand_host.h:
+      the plus strand of seeqdevScanRunStrands, the right flank of seeqdevScanRunInserts) */
+   seeqdev_hit_t *side_rec; uint64_t *side_off; size_t cap_side;
    /* seeqdevScanRunStrands (seeq_strand.h): allocated by the first both-strands call */
-   seeqdev_hit_t *st_side; uint64_t *st_side_off; size_t cap_st_side;      /* two scans: the plus records and offsets, aside while the twin is scanned */
    uint4    *st_mrg; uint64_t *st_mrg_off; uint32_t *st_bsum; size_t cap_st_mrg;      /* the merged records and offsets, the reduction's per-tile sums */
    StrandCnt *d_stcnt, *h_stcnt;                          /* h_ pinned */
    hipEvent_t ev_st[2]; bool have_st_ev; float st_merge_ms;      /* profiling: around the merge's launches and copies (the FASTQ filter not included) */
+   /* seeqdevScanRunInserts (seeq_insert.h): allocated by the first inserts call; the result (ins_rec, ins_off, ins_pos) is valid until the next one */
+   uint4    *ins_jn; uint32_t *ins_bsum; uint64_t *ins_bbytes; size_t cap_ins_jn;      /* the joined records (one per left record), the reduction's per-tile sums */
+   uint4    *ins_rec; uint64_t *ins_off, *ins_pos; size_t cap_ins;      /* the insert records, their line offsets, their byte positions in the insert text */
+   InsertCnt *d_inscnt, *h_inscnt;                        /* h_ pinned */
+   size_t    ins_n;                                       /* records of the last inserts call */
+   uint64_t  ins_text_bytes;                              /* bytes of its insert text */
+   bool      ins_staged; size_t ins_staged_nbytes;        /* it scanned the context's staged text (seeqdevScanHostInserts), and d_text still holds it */
+   hipEvent_t ev_ins[2]; bool have_ins_ev; float ins_join_ms;      /* profiling: around the join's launches */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -620,6 +633,7 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
    (void)use_device(s->device);
    if (s->have_h2d_ev) { (void)hipEventDestroy(s->ev_h2d[0]); (void)hipEventDestroy(s->ev_h2d[1]); }
    if (s->have_st_ev) { (void)hipEventDestroy(s->ev_st[0]); (void)hipEventDestroy(s->ev_st[1]); }
+   if (s->have_ins_ev) { (void)hipEventDestroy(s->ev_ins[0]); (void)hipEventDestroy(s->ev_ins[1]); }
    (void)hipStreamSynchronize(s->stream);
    ws_free_all(&s->ws);
    multi_plan_free(s->mplan);
@@ -1694,6 +1708,7 @@ static int text_upload(seeqdev_scan *s, const char *host_text, size_t nbytes, bo
    if (nbytes) HIP_TRY(hipMemcpyAsync(s->d_text, host_text, nbytes, hipMemcpyHostToDevice, s->stream), EIO);
    if (timed) HIP_TRY(hipEventRecord(s->ev_h2d[1], s->stream), EIO);
    s->avg_text = NULL;
+   s->ins_staged = false;                                  /* (seeqdevScanInsertText: the staged text of the last inserts call is gone) */
    return 0;
 }
 
@@ -1731,6 +1746,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 #include "seeq_multi_host.h"
 #include "seeq_demux_host.h"
 #include "seeq_strand_host.h"
+#include "seeq_insert_host.h"
 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {

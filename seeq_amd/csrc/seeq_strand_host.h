@@ -40,11 +40,16 @@ static const seeqdev_pattern *pattern_twin(const seeqdev_pattern *pat)
 /* the reduction's per-tile sums for n merged records (seeq_strand.h: kept, opened, minus per tile) */
 static size_t strand_bsum_words(size_t n) { return 3 * (n / SEEQ_STRAND_TILE + 2); }
 
-/* Room for the plus records of a two-scan call (16 + 8 bytes per record), kept aside while the twin is scanned. */
-static int strands_ws_side(seeqdev_scan *s, size_t n)
+/* The first n records of the scan just fetched, with their offsets, copied aside on the device (16 + 8 bytes per record) before the call's
+   next scan overwrites them: the one owner of the side copy (the both-strands call's plus records, the inserts call's right records).  Waits. */
+static int side_keep(seeqdev_scan *s, size_t n)
 {
-   if (n < 1) n = 1;
-   return ws_grow(&s->ws, &s->cap_st_side, n, {{s->st_side, n * sizeof(seeqdev_hit_t)}, {s->st_side_off, n * sizeof(uint64_t)}});
+   if (!n) return 0;
+   if (ws_grow(&s->ws, &s->cap_side, n, {{s->side_rec, n * sizeof(seeqdev_hit_t)}, {s->side_off, n * sizeof(uint64_t)}})) return -1;
+   HIP_TRY(hipMemcpyAsync(s->side_rec, s->records, n * sizeof(seeqdev_hit_t), hipMemcpyDeviceToDevice, s->stream), EIO);
+   HIP_TRY(hipMemcpyAsync(s->side_off, s->rec_off, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s->stream), EIO);
+   HIP_TRY(hipStreamSynchronize(s->stream), EIO);            /* the next scan may reallocate the records the copies read */
+   return 0;
 }
 
 /* Room for n merged records.  Nothing on the stream reads the old blocks: every strands call ends synchronised. */
@@ -64,7 +69,7 @@ struct StrandSrc {
    seeqdev_counts_t plus;             /* the plus scan's counts: nlines, nheaders */
 };
 
-/* Two scans: the plus records (with their offsets) are copied aside on the device before the twin's scan overwrites them. */
+/* Two scans: the plus records (with their offsets) are copied aside on the device (side_keep) before the twin's scan overwrites them. */
 static int strands_two_scans(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, const seeqdev_pattern_t *twin, const void *d_text, size_t nbytes,
                              int opts, StrandSrc *src)
 {
@@ -73,13 +78,7 @@ static int strands_two_scans(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, co
    if (seeqdevScanFetch(s, &src->plus)) return -1;
    src->na = src->plus.nrecords;
    if (src->na > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
-   if (src->na) {
-      const size_t na = (size_t)src->na;
-      if (strands_ws_side(s, na)) return -1;
-      HIP_TRY(hipMemcpyAsync(s->st_side, s->records, na * sizeof(seeqdev_hit_t), hipMemcpyDeviceToDevice, s->stream), EIO);
-      HIP_TRY(hipMemcpyAsync(s->st_side_off, s->rec_off, na * sizeof(uint64_t), hipMemcpyDeviceToDevice, s->stream), EIO);
-      HIP_TRY(hipStreamSynchronize(s->stream), EIO);         /* the next scan may reallocate the records the copies read */
-   }
+   if (side_keep(s, (size_t)src->na)) return -1;
    if (seeqdevScanRun(s, twin, d_text, nbytes, opts, SEEQDEV_WANT_RECORDS)) return -1;
    if (seeqdevScanFetch(s, &cb)) return -1;
    if (cb.nlines != src->plus.nlines) {
@@ -89,7 +88,7 @@ static int strands_two_scans(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, co
       return -1;
    }
    src->nb = cb.nrecords;
-   src->a = s->st_side; src->a_off = s->st_side_off;
+   src->a = s->side_rec; src->a_off = s->side_off;
    src->b = s->records; src->b_off = s->rec_off;
    return 0;
 }

@@ -346,6 +346,70 @@ class Scanner:
         return self._strands(lambda cnt, per: self._lib.seeqdevScanRunStrands(self._h, pattern.handle, C.c_void_p(t.data_ptr()), t.numel(), options, want,
                                                                              cnt, per), want, copy)
 
+    # ---- the insert between two flanks (include/seeq_amd.h: seeqdevScanRunInserts / seeqdevScanHostInserts) ----
+    def _inserts(self, call, copy):
+        cnt = _capi.seeqdev_insert_counts_t()
+        _check(call(C.byref(cnt)))
+        res = dict(nlines=int(cnt.nlines), nleft=int(cnt.nleft), nright=int(cnt.nright), nboth=int(cnt.nboth), ninserts=int(cnt.ninserts),
+                   text_bytes=int(cnt.text_bytes))
+        if copy:
+            res["records"] = self.insert_records(res["ninserts"])
+        return res
+
+    def inserts_host(self, left, right, data, options=0, min_len=0, max_len=0):
+        """data: bytes, staged once.  Per line the insert between the `left` flank's record (options: SQ_BEST or SQ_FIRST) and the chosen
+        occurrence of the `right` flank at min_len .. max_len bytes behind it (max_len 0: no upper bound), joined on the device
+        (seeq_amd.h) -> dict: nlines, nleft, nright, nboth, ninserts, text_bytes, records (INSERT_DTYPE, in line order).
+        insert_offsets() serves the records' line offsets, insert_text() the inserts themselves.  options may hold SEEQDEV_FASTA or
+        SEEQDEV_FASTQ."""
+        return self._inserts(lambda cnt: self._lib.seeqdevScanHostInserts(self._h, left.handle, right.handle, data, len(data), options, min_len, max_len, cnt), True)
+
+    def inserts_tensor(self, left, right, t, options=0, min_len=0, max_len=0, copy=True):
+        """t: torch uint8 CUDA tensor (contiguous), resident.  As inserts_host; copy=False leaves the records on the device
+        (inserts_device_ptr / insert_records)."""
+        return self._inserts(lambda cnt: self._lib.seeqdevScanRunInserts(self._h, left.handle, right.handle, C.c_void_p(t.data_ptr()), t.numel(), options,
+                                                                         min_len, max_len, cnt), copy)
+
+    def insert_records(self, n, first=0):
+        """Copy records [first, first + n) of the last inserts call to the host -> structured array of INSERT_DTYPE."""
+        out = np.zeros(n, dtype=INSERT_DTYPE)
+        _check(self._lib.seeqdevScanCopyInserts(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def insert_offsets(self, n, first=0):
+        """Per insert record: byte offset of its line in the scanned buffer -> ndarray [n] u64."""
+        out = np.zeros(n, dtype=np.uint64)
+        _check(self._lib.seeqdevScanCopyInsertOffsets(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def inserts_device_ptr(self):
+        """Device address of the last inserts call's records (seeqdev_insert_t, in line order; valid until this Scanner's next inserts call)."""
+        return self._lib.seeqdevScanInsertsDevice(self._h)
+
+    def insert_text_bytes(self):
+        """Size of the last inserts call's insert text (seeqdevScanInsertText's size query)."""
+        n = C.c_uint64(0)
+        _check(self._lib.seeqdevScanInsertText(self._h, None, 0, None, 0, C.byref(n)))
+        return int(n.value)
+
+    def insert_text(self, t=None):
+        """The inserts of the last call cut out of its text on the device: every insert followed by a newline, in record order.
+        t: the tensor inserts_tensor scanned -> a torch uint8 tensor on t's device (the next stage's input: scan_tensor,
+        demux_tensor); None: the text inserts_host staged -> bytes."""
+        import torch
+        n = self.insert_text_bytes()
+        out = torch.empty(n, dtype=torch.uint8, device=t.device if t is not None else "cuda")
+        got = C.c_uint64(0)
+        _check(self._lib.seeqdevScanInsertText(self._h, C.c_void_p(t.data_ptr()) if t is not None else None, t.numel() if t is not None else 0,
+                                               C.c_void_p(out.data_ptr()) if n else None, n, C.byref(got)))
+        return out if t is not None else out.cpu().numpy().tobytes()
+
+    def last_inserts_join_ms(self):
+        """Device time of the last inserts call's join (its four launches; profiling on), 0 when not measured."""
+        ms = C.c_float(0)
+        _check(self._lib.seeqdevScanLastInsertsMs(self._h, C.byref(ms)))
+        return float(ms.value)
+
     # ---- several patterns, one text (include/seeq_amd.h: seeqdevScanRunMulti / seeqdevScanHostMulti) ----
     def _multi(self, patterns, call, want, copy=True):
         n = len(patterns)
@@ -427,6 +491,9 @@ FALLBACK_NO_STREAM, FALLBACK_NONDNA, FALLBACK_LONG_LINES, FALLBACK_SEAM, FALLBAC
 
 # One record of seeqdevScanRunStrands as strand_records() returns it: the 16-byte seeqdev_hit_t with the strand bit of `dist` taken out.
 STRAND_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("dist", "<u4"), ("strand", "u1")])
+
+# One record of seeqdevScanRunInserts (seeq_amd.h: seeqdev_insert_t, 16 bytes): bytes [start, end) of line `line` are the insert.
+INSERT_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("ldist", "<u2"), ("rdist", "<u2")])
 
 # One record of seeqdevScanRunDemux (seeq_amd.h: seeqdev_demux_t, 16 bytes).
 DEMUX_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("dist", "<u2"), ("pattern", "u1"), ("margin", "u1")])
