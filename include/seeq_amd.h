@@ -369,6 +369,66 @@ int seeqdevScanInsertText(seeqdev_scan_t * scan, const void * d_text, size_t nby
  * otherwise, and when there was nothing to join). */
 int seeqdevScanLastInsertsMs(const seeqdev_scan_t * scan, float * join_ms);
 
+/* THE TALLY OF DISTINCT SPANS.  Inserts are cut in order to count them -- guide counts of a screen, barcode abundance, UMI families --
+ * and the demultiplexer names the best of a few patterns per line, not how often each distinct sequence occurs.  seeqdevScanTally counts
+ * the distinct sequences among the spans of a record array ON THE DEVICE (seeq_tally.h), where they lie in the resident text: no insert
+ * text is gathered, nothing but the table goes to the host.
+ *   source               SEEQDEV_TALLY_INSERTS: bytes [start, end) of the records of the context's last inserts call;
+ *                        SEEQDEV_TALLY_HITS: bytes [start, end) of the records seeqdevScanCopyRecords serves now -- those of a plain scan
+ *                        fetched with SEEQDEV_WANT_RECORDS, or of a both-strands call.  A minus-strand hit is tallied as the bytes of
+ *                        the text, NOT reverse-complemented.
+ *   key                  of a span of L <= SEEQDEV_TALLY_MAX_LEN bases, every byte one of ACGTUacgtu:
+ *                        (1 << 2L) | sum of code(b_i) << 2(L - 1 - i), code = (ASCII >> 1) & 3 as in the packed batches below
+ *                        (A 0, C 1, T/U 2, G 3).  The leading 1 carries the length: the empty span has key 1; bit 63 is never set;
+ *                        no key is 0.  Lower case is tallied as its base, U as T.
+ *   THE TABLE'S ORDER    one seeqdev_tally_t per distinct key, keys ascending: by length first, then base by base with A < C < T < G.
+ *                        (Ordering by count is a stable argsort of the copied counts on the host.)
+ *   not tallied          a span of more than 31 bases is LONG, one with another byte (N included) is FOREIGN; each kind is counted,
+ *                        a span that is both counts as long.  nspans = ntallied + nlong + nforeign, and the table's counts sum to
+ *                        ntallied.
+ * d_text / nbytes: the text the records were found in.  d_text == NULL is legal for SEEQDEV_TALLY_INSERTS only: the context's staged
+ * text of the last seeqdevScanHostInserts, as seeqdevScanInsertText (EINVAL when another host call has staged over it since).
+ * Under SEEQDEV_FASTQ and after a both-strands call nothing special applies: the offsets are those of the sequence lines in the
+ * original buffer.  Synchronous.  The call reads the record arrays and writes arrays of its own: the inserts result
+ * (seeqdevScanInsertText included), the record arrays and the context's fetch state are afterwards what they were.  The table --
+ * seeqdevScanTallyDevice / seeqdevScanCopyTally -- is valid until the context's next tally or seeqdevScanFree.
+ * EINVAL, before any device call: NULL scan / counts, an unknown source, NULL text with bytes, SEEQDEV_TALLY_INSERTS without a completed
+ * inserts call, SEEQDEV_TALLY_HITS without text, on a context with nothing fetched (fresh, or after a multi, demux or inserts call,
+ * which leave nothing to fetch) or after a packed scan (its offsets are no offsets into a text).  EIO: a span with end < start or one
+ * that reaches beyond nbytes (checked before any byte of it is loaded; the context stays usable), or an internal inconsistency.
+ * E2BIG: more than 2^32 - 1 spans.
+ * Device memory of its own (allocated by a context's first tally, freed with it): 17 bytes per span (two 8-byte key arrays, a
+ * 1 KiB digit matrix per tile of 1 024 spans) plus 25 bytes per tile, and 16 bytes per distinct key.
+ * seeqdevTallyKey / seeqdevTallyDecode: the rule's two directions on the host, no GPU needed.  Key: -1 / EINVAL for a long or foreign
+ * sequence.  Decode: writes the bases in upper case by code (A C T G) and a terminating 0, returns L; -1 / EINVAL for a value that
+ * is no key (0, bit 63 set, a leading 1 at an odd bit).  (The reference counts nothing: an addition of this boundary.) */
+#define SEEQDEV_TALLY_INSERTS 0   /* the spans of the context's last inserts call */
+#define SEEQDEV_TALLY_HITS    1   /* [start, end) of the records seeqdevScanCopyRecords would serve now */
+#define SEEQDEV_TALLY_MAX_LEN 31
+typedef struct {
+   uint64_t key;
+   uint64_t count;
+} seeqdev_tally_t;   /* 16 bytes */
+
+typedef struct {
+   uint64_t nspans;      /* records of the source */
+   uint64_t ntallied;    /* spans with a key: the sum of the table's counts */
+   uint64_t nlong;       /* spans of more than SEEQDEV_TALLY_MAX_LEN bytes */
+   uint64_t nforeign;    /* spans of at most that many with a byte that is no base */
+   uint64_t ndistinct;   /* entries of the table */
+   uint32_t max_len;     /* the largest tallied length */
+   uint32_t passes;      /* passes of the sort: ceil((2 * max_len + 1) / 8); 0: nothing was tallied */
+} seeqdev_tally_counts_t;
+
+int seeqdevScanTally(seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_counts_t * counts);
+const seeqdev_tally_t * seeqdevScanTallyDevice(const seeqdev_scan_t * scan);
+int seeqdevScanCopyTally(seeqdev_scan_t * scan, seeqdev_tally_t * host_out, size_t first, size_t n);
+/* Device time (ms) of the last tally -- its launches and counter copies, between two HIP events on the context's stream (profiling on;
+ * 0 otherwise, and when there was no span). */
+int seeqdevScanLastTallyMs(const seeqdev_scan_t * scan, float * ms);
+int seeqdevTallyKey(const char * seq, size_t len, uint64_t * key);
+int seeqdevTallyDecode(uint64_t key, char out[32]);
+
 /* PACKED READ BATCHES -- 2 bits per base instead of a byte: a quarter of the HBM (and PCIe) traffic of the ASCII scan for
  * read sets that are kept packed anyway (BAM, .2bit, a sequencer's own format).  Layout, all device pointers:
  *   bases : four bases per byte, the FIRST base of a byte in its bits 7-6; code = (ASCII >> 1) & 3, i.e. A 0, C 1, T/U 2, G 3;

@@ -77,6 +77,17 @@ class seeqdev_insert_counts_t(C.Structure):
                 ("text_bytes", C.c_uint64)]
 
 
+class seeqdev_tally_t(C.Structure):
+    _fields_ = [("key", C.c_uint64), ("count", C.c_uint64)]
+
+
+class seeqdev_tally_counts_t(C.Structure):
+    _fields_ = [("nspans", C.c_uint64), ("ntallied", C.c_uint64), ("nlong", C.c_uint64), ("nforeign", C.c_uint64), ("ndistinct", C.c_uint64),
+                ("max_len", C.c_uint32), ("passes", C.c_uint32)]
+
+
+SEEQDEV_TALLY_INSERTS, SEEQDEV_TALLY_HITS, SEEQDEV_TALLY_MAX_LEN = 0, 1, 31
+
 # Every symbol the three public headers declare (tests check the .so exports all of them).
 EXPORTS = [
     # libseeq.h
@@ -96,6 +107,7 @@ EXPORTS = [
     "seeqdevPatternRevComp", "seeqdevScanRunStrands", "seeqdevScanHostStrands", "seeqdevScanLastStrandsMs",
     "seeqdevScanRunInserts", "seeqdevScanHostInserts", "seeqdevScanInsertsDevice", "seeqdevScanCopyInserts", "seeqdevScanCopyInsertOffsets",
     "seeqdevScanInsertText", "seeqdevScanLastInsertsMs",
+    "seeqdevScanTally", "seeqdevScanTallyDevice", "seeqdevScanCopyTally", "seeqdevScanLastTallyMs", "seeqdevTallyKey", "seeqdevTallyDecode",
     "seeqdevScanLastRuns", "seeqdevScanFallback",
 ]
 
@@ -256,6 +268,18 @@ def lib():
     L.seeqdevScanInsertText.restype = C.c_int
     L.seeqdevScanLastInsertsMs.argtypes = [C.c_void_p, P(C.c_float)]
     L.seeqdevScanLastInsertsMs.restype = C.c_int
+    L.seeqdevScanTally.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(seeqdev_tally_counts_t)]
+    L.seeqdevScanTally.restype = C.c_int
+    L.seeqdevScanTallyDevice.argtypes = [C.c_void_p]
+    L.seeqdevScanTallyDevice.restype = C.c_void_p
+    L.seeqdevScanCopyTally.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+    L.seeqdevScanCopyTally.restype = C.c_int
+    L.seeqdevScanLastTallyMs.argtypes = [C.c_void_p, P(C.c_float)]
+    L.seeqdevScanLastTallyMs.restype = C.c_int
+    L.seeqdevTallyKey.argtypes = [C.c_char_p, C.c_size_t, P(C.c_uint64)]
+    L.seeqdevTallyKey.restype = C.c_int
+    L.seeqdevTallyDecode.argtypes = [C.c_uint64, C.c_char_p]
+    L.seeqdevTallyDecode.restype = C.c_int
     L.seeqdevScanPacked.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(seeqdev_packed_t), C.c_int, C.c_int]
     L.seeqdevScanPacked.restype = C.c_int
     L.seeqdevPackReads.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]

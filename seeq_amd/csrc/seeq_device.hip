@@ -23,7 +23,7 @@
  * Here: plumbing, pattern handle, scan context, the segment and packed drivers, the scan
  * entries.  The side entries are included where they belong in that order: seeq_synth.h,
  * seeq_text_alloc.h, seeq_multi_host.h, seeq_demux_host.h, seeq_strand_host.h, seeq_insert_host.h,
- * seeq_string.h.
+ * seeq_tally_host.h, seeq_string.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -109,8 +109,10 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_fastq.h"
 #include "seeq_strand.h"
 #include "seeq_insert.h"
+#include "seeq_tally.h"
 static_assert(sizeof(seeqdev_demux_t) == 16 && sizeof(seeqdev_hit_t) == sizeof(uint4), "demux records are written as uint4");
 static_assert(sizeof(seeqdev_insert_t) == sizeof(uint4), "insert records are written as uint4");
+static_assert(sizeof(seeqdev_tally_t) == sizeof(uint4) && SEEQ_TALLY_LEN_MAX == SEEQDEV_TALLY_MAX_LEN, "tally entries are written as uint4");
 #include "seeq_post.h"
 static_assert(STREAM_NW == STREAM_NW_HOST, "waves per k_stream workgroup");
 extern "C" {
@@ -512,6 +514,13 @@ struct seeqdev_scan {
    uint64_t  ins_text_bytes;                              /* bytes of its insert text */
    bool      ins_staged; size_t ins_staged_nbytes;        /* it scanned the context's staged text (seeqdevScanHostInserts), and d_text still holds it */
    hipEvent_t ev_ins[2]; bool have_ins_ev; float ins_join_ms;      /* profiling: around the join's launches */
+   bool      ins_done;                                    /* an inserts call has completed: ins_n records (none included) are a result */
+   /* seeqdevScanTally (seeq_tally.h): allocated by the first tally; the table (tl_tab, tl_n) is valid until the next one */
+   uint64_t *tl_key0, *tl_key1; uint32_t *tl_mat, *tl_sum; uint4 *tl_stat; size_t cap_tl;      /* per span: the two key arrays; per tile: the digit matrix, the sums, the pack's numbers */
+   seeqdev_tally_t *tl_tab; size_t cap_tl_tab;            /* the table: one entry per distinct key */
+   TallyCnt *d_tlcnt, *h_tlcnt;                           /* h_ pinned */
+   size_t    tl_n;                                        /* entries of the last tally's table */
+   hipEvent_t ev_tl[2]; bool have_tl_ev; float tl_ms;     /* profiling: around the tally's launches and counter copies */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -634,6 +643,7 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
    if (s->have_h2d_ev) { (void)hipEventDestroy(s->ev_h2d[0]); (void)hipEventDestroy(s->ev_h2d[1]); }
    if (s->have_st_ev) { (void)hipEventDestroy(s->ev_st[0]); (void)hipEventDestroy(s->ev_st[1]); }
    if (s->have_ins_ev) { (void)hipEventDestroy(s->ev_ins[0]); (void)hipEventDestroy(s->ev_ins[1]); }
+   if (s->have_tl_ev) { (void)hipEventDestroy(s->ev_tl[0]); (void)hipEventDestroy(s->ev_tl[1]); }
    (void)hipStreamSynchronize(s->stream);
    ws_free_all(&s->ws);
    multi_plan_free(s->mplan);
@@ -1747,6 +1757,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 #include "seeq_demux_host.h"
 #include "seeq_strand_host.h"
 #include "seeq_insert_host.h"
+#include "seeq_tally_host.h"
 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {

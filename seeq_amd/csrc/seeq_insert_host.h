@@ -145,6 +145,7 @@ static int inserts_entry(seeqdev_scan_t *s, const seeqdev_pattern_t *left, const
    s->ins_n = 0;                                           /* (the result of the call before is gone, whatever comes of this one) */
    s->ins_text_bytes = 0;
    s->ins_staged = false;
+   s->ins_done = false;
    s->ins_join_ms = 0.f;
    seeqdev_insert_counts_t c;
    const int rc = inserts_run(s, left, right, d_text, nbytes, options, min_len, max_len, &c);
@@ -154,6 +155,7 @@ static int inserts_entry(seeqdev_scan_t *s, const seeqdev_pattern_t *left, const
    s->ins_text_bytes = c.text_bytes;
    s->ins_staged = staged;
    s->ins_staged_nbytes = nbytes;
+   s->ins_done = true;
    *counts = c;
    return 0;
 }

@@ -410,6 +410,41 @@ class Scanner:
         _check(self._lib.seeqdevScanLastInsertsMs(self._h, C.byref(ms)))
         return float(ms.value)
 
+    # ---- the tally of distinct spans (include/seeq_amd.h: seeqdevScanTally) ----
+    def tally(self, t=None, source="inserts", copy=True):
+        """How often each distinct sequence occurs among the inserts of the last inserts call (source "inserts") or among the matches
+        [start, end) of the records this Scanner serves now (source "hits": a fetched scan with WANT_RECORDS, a both-strands call),
+        counted on the device.  t: the torch uint8 CUDA tensor those records were found in; None (inserts only): the text inserts_host
+        staged.  -> dict: nspans, ntallied, nlong, nforeign, ndistinct, max_len, passes; copy adds keys and counts, uint64 arrays in
+        ascending key order (by length, then A < C < T < G): tally_key / tally_decode / tally_lookup.  copy=False leaves the table on
+        the device (tally_device_ptr / tally_table)."""
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS}.get(source, source)
+        cnt = _capi.seeqdev_tally_counts_t()
+        _check(self._lib.seeqdevScanTally(self._h, src, C.c_void_p(t.data_ptr()) if t is not None else None, t.numel() if t is not None else 0, C.byref(cnt)))
+        res = dict(nspans=int(cnt.nspans), ntallied=int(cnt.ntallied), nlong=int(cnt.nlong), nforeign=int(cnt.nforeign), ndistinct=int(cnt.ndistinct),
+                   max_len=int(cnt.max_len), passes=int(cnt.passes))
+        if copy:
+            tab = self.tally_table(res["ndistinct"])
+            res["keys"] = np.ascontiguousarray(tab["key"])
+            res["counts"] = np.ascontiguousarray(tab["count"])
+        return res
+
+    def tally_table(self, n, first=0):
+        """Copy entries [first, first + n) of the last tally's table to the host -> structured array of TALLY_DTYPE."""
+        out = np.zeros(n, dtype=TALLY_DTYPE)
+        _check(self._lib.seeqdevScanCopyTally(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def tally_device_ptr(self):
+        """Device address of the last tally's table (seeqdev_tally_t, ascending keys; valid until this Scanner's next tally)."""
+        return self._lib.seeqdevScanTallyDevice(self._h)
+
+    def last_tally_ms(self):
+        """Device time of the last tally (its launches and counter copies; profiling on), 0 when not measured."""
+        ms = C.c_float(0)
+        _check(self._lib.seeqdevScanLastTallyMs(self._h, C.byref(ms)))
+        return float(ms.value)
+
     # ---- several patterns, one text (include/seeq_amd.h: seeqdevScanRunMulti / seeqdevScanHostMulti) ----
     def _multi(self, patterns, call, want, copy=True):
         n = len(patterns)
@@ -494,6 +529,41 @@ STRAND_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("di
 
 # One record of seeqdevScanRunInserts (seeq_amd.h: seeqdev_insert_t, 16 bytes): bytes [start, end) of line `line` are the insert.
 INSERT_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("ldist", "<u2"), ("rdist", "<u2")])
+
+# One entry of seeqdevScanTally's table (seeq_amd.h: seeqdev_tally_t, 16 bytes).
+TALLY_DTYPE = np.dtype([("key", "<u8"), ("count", "<u8")])
+
+
+def tally_key(seq):
+    """The tally's key of a sequence of at most 31 bases ACGTU in either case (str or bytes); ValueError for a long or foreign one."""
+    raw = seq.encode("latin-1") if isinstance(seq, str) else bytes(seq)
+    key = C.c_uint64(0)
+    if _capi.lib().seeqdevTallyKey(raw, len(raw), C.byref(key)):
+        raise ValueError("no tally key: %r is longer than 31 bases or holds a byte that is no base" % (seq,))
+    return int(key.value)
+
+
+def tally_decode(key):
+    """The sequence a tally key stands for, upper case (A C T G); ValueError for a value that is no key."""
+    out = C.create_string_buffer(32)
+    n = _capi.lib().seeqdevTallyDecode(int(key), out)
+    if n < 0:
+        raise ValueError("no tally key: %#x" % int(key))
+    return out.raw[:n].decode("ascii")
+
+
+def tally_lookup(result, sequences):
+    """One count per given sequence from a tally() result (copy=True): a binary search over the key-ordered table, 0 when the
+    sequence was not seen -- the count table of a guide or barcode library.  Host NumPy over the distinct keys only."""
+    keys, counts = result["keys"], result["counts"]
+    want = np.array([tally_key(q) for q in sequences], dtype=np.uint64)
+    out = np.zeros(len(want), dtype=np.uint64)
+    if len(keys) and len(want):
+        at = np.minimum(np.searchsorted(keys, want), len(keys) - 1)
+        hit = keys[at] == want
+        out[hit] = counts[at[hit]]
+    return out
+
 
 # One record of seeqdevScanRunDemux (seeq_amd.h: seeqdev_demux_t, 16 bytes).
 DEMUX_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("dist", "<u2"), ("pattern", "u1"), ("margin", "u1")])
