@@ -137,6 +137,14 @@ int seeqdevScanLastPath(const seeqdev_scan_t * scan);
 /* 1 when the last run's k_stream walked a partition FILTER automaton (candidates verified by the exact pass)
  * instead of the pattern's complete automaton. */
 int seeqdevScanLastFilter(const seeqdev_scan_t * scan);
+/* The plan the last run executed (seeq_plan.h: which kernel instance scanned, which post-pass followed), as sixteen numbers:
+ * rc, path (as seeqdevScanLastPath), fw (words of the one-pass kernels' column), use_stream, use_pair, use_myers, filter, stream_ll,
+ * stream_sub (0, 1 SQ_CONVERT, 2 SQ_IGNORE), stream_wu (warm-up dwords of the scan kernel), verify, order2, leaders, window_ok,
+ * ll_filter (0, 1 the absorbing table, 2 the restart table / k_pair's long-line windows), skip_back.  Like seeqdevScanLastPath it
+ * describes the run that produced the fetched result: after a fall-back re-run, the re-run's plan.  A packed run (path 8) has no
+ * such plan: path and filter are set, the rest is 0.  All 0 before the first scan.  Read-only, for tests and diagnostics: the
+ * numbers follow the planner and may change with it.  0, or -1 (EINVAL) for a NULL argument. */
+int seeqdevScanLastPlan(const seeqdev_scan_t * scan, int out[16]);
 /* 1 when the last packed run (path 8) walked the pattern's QUAD table -- four bases, one packed byte, per table step over a small
  * partition-filter automaton (seeq_dfa.h section 3b) -- instead of the pair table (two bases per step). */
 int seeqdevScanLastPackedQuad(const seeqdev_scan_t * scan);

@@ -108,7 +108,7 @@ EXPORTS = [
     "seeqdevScanRunInserts", "seeqdevScanHostInserts", "seeqdevScanInsertsDevice", "seeqdevScanCopyInserts", "seeqdevScanCopyInsertOffsets",
     "seeqdevScanInsertText", "seeqdevScanLastInsertsMs",
     "seeqdevScanTally", "seeqdevScanTallyDevice", "seeqdevScanCopyTally", "seeqdevScanLastTallyMs", "seeqdevTallyKey", "seeqdevTallyDecode",
-    "seeqdevScanLastRuns", "seeqdevScanFallback",
+    "seeqdevScanLastRuns", "seeqdevScanFallback", "seeqdevScanLastPlan",
 ]
 
 
@@ -220,6 +220,8 @@ def lib():
     L.seeqdevScanLastPath.restype = C.c_int
     L.seeqdevScanLastFilter.argtypes = [C.c_void_p]
     L.seeqdevScanLastFilter.restype = C.c_int
+    L.seeqdevScanLastPlan.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.seeqdevScanLastPlan.restype = C.c_int
     L.seeqdevScanLastPackedQuad.argtypes = [C.c_void_p]
     L.seeqdevScanLastPackedQuad.restype = C.c_int
     L.seeqdevScanLastRuns.argtypes = [C.c_void_p]

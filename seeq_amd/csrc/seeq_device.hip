@@ -434,6 +434,7 @@ struct seeqdev_scan {
    ScanKnobs   knobs;
    OccMemo     occ[8]; int nocc;  /* hipOccupancyMaxActiveBlocksPerMultiprocessor results */
    bool        last_filter;       /* the last run walked a partition filter automaton */
+   int         last_plan[16];     /* the last run's plan, as seeqdevScanLastPlan reports it (run_setup; a packed run: path 8 alone) */
    bool        last_packed_quad;  /* the last packed run walked the quad table */
    size_t      pk_seg_reads;      /* reads per segment of a packed run */
    Workspace   ws;                /* owns every device and page-locked buffer below: ws_grow / ws_make bring them into being, ws_free_all ends them */
@@ -732,6 +733,12 @@ extern "C" int seeqdevScanSetLineHint(seeqdev_scan_t *s, double avg_bytes_per_li
 
 extern "C" int seeqdevScanLastPath(const seeqdev_scan_t *s) { return s ? s->last_path : 0; }
 extern "C" int seeqdevScanLastFilter(const seeqdev_scan_t *s) { return s && s->last_filter ? 1 : 0; }
+extern "C" int seeqdevScanLastPlan(const seeqdev_scan_t *s, int out[16])
+{
+   if (!s || !out) { errno = EINVAL; return -1; }
+   memcpy(out, s->last_plan, sizeof s->last_plan);
+   return 0;
+}
 extern "C" int seeqdevScanLastPackedQuad(const seeqdev_scan_t *s) { return s && s->last_packed_quad ? 1 : 0; }
 extern "C" int seeqdevScanLastRuns(const seeqdev_scan_t *s) { return s ? s->last_runs : 0; }
 
@@ -952,6 +959,11 @@ static int run_setup(seeqdev_scan *s, SegRun &r)
    }
    s->last_path = plan.path;
    s->last_filter = plan.filter;
+   {  /* (the numbers and the order of tests/host_harness.cpp: harness_plan) */
+      const int v[16] = {plan.rc, plan.path, plan.fw, plan.use_stream, plan.use_pair, plan.use_myers, plan.filter, plan.stream_ll, plan.stream_sub, plan.stream_wu,
+                         plan.verify, plan.order2, plan.leaders, plan.window_ok, plan.ll_restart ? 2 : (plan.ll_filter ? 1 : 0), (int)plan.skip_back};
+      memcpy(s->last_plan, v, sizeof v);
+   }
 
    const size_t nbytes = s->nbytes;
    r.seg_bytes = single ? (nbytes ? nbytes : 1) : s->seg_bytes;
@@ -1367,6 +1379,8 @@ static int run_packed(seeqdev_scan *s)
    HIP_TRY(hipMemcpyAsync(s->h_cnt, c, sizeof(Counters), hipMemcpyDeviceToHost, st), EIO);
    s->last_path = 8;
    s->last_filter = true;
+   memset(s->last_plan, 0, sizeof s->last_plan);
+   s->last_plan[1] = 8; s->last_plan[6] = 1;                /* (no ScanPlan behind a packed run: its path and the filter flag) */
    return 0;
 }
 

@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void k_bounds2(ScanArgs a, uint4 *ent, uint32_
          /* windows: the line's first candidate belongs to the segment before this one, whose exact pass could not know of this
             one -- the run is void, the next one scans candidate lines to their ends (seeqdevScanFetch).  (SQ_IGNORE: every segment's first
             line end comes with a marker made unseen -- it counts only when the line really holds a skipped byte and enough characters.) */
-         if (a.window_ok && e.y == prev0) {
+         if (a.window_ok && e.y == prev0 && !a.first_seg) {      /* (the first segment has none before it: FASTA counts the text's first header as line 0, which is what prev0 starts as) */
             bool voids = true;
             if (a.ig_thr && (e.w & 2u) && unresolved) {
                const uint64_t hp0 = a.seg_base + e.x;

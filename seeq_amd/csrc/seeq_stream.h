@@ -736,7 +736,7 @@ __global__ __launch_bounds__(256) void k_stream_bounds(ScanArgs a, uint32_t *hit
          hit_col[k] = (a.nh[k] & 1u) ? a.hit_start[k] : a.hit_start[k] + hit_col[k];
          /* k_pair, windows: the line's first candidate belongs to the segment before this one, whose exact pass could not
             know of this one -- the run is void, the next one scans candidate lines to their ends (seeqdevScanFetch) */
-         if (a.window_ok && ln == c->prev_hit_line) atomicOr(&c->overflow, OVF_SEAM);
+         if (a.window_ok && ln == c->prev_hit_line && !a.first_seg) atomicOr(&c->overflow, OVF_SEAM);      /* (no segment before the first: see k_bounds2) */
          a.hit_start[k] = 0xFFFFFFFFu;
          continue;
       }

@@ -180,6 +180,11 @@ class RevCompPattern:
             pass
 
 
+# the sixteen numbers of seeqdevScanLastPlan (and of tests/host_harness.cpp: harness_plan), in order
+PLAN_FIELDS = ("rc", "path", "fw", "use_stream", "use_pair", "use_myers", "filter", "stream_ll", "stream_sub", "stream_wu", "verify", "order2",
+               "leaders", "window_ok", "ll_filter", "skip_back")
+
+
 class Scanner:
     def __init__(self, stream=None):
         """stream: a hipStream_t as int (e.g. torch.cuda.current_stream().cuda_stream) or None.  None and 0 (torch's
@@ -219,6 +224,13 @@ class Scanner:
     def last_filter(self):
         """True when the last k_stream run walked a partition filter automaton (candidates verified by the exact pass)."""
         return bool(self._lib.seeqdevScanLastFilter(self._h))
+
+    def last_plan(self):
+        """The plan the last run executed (seeqdevScanLastPlan) as a dict over PLAN_FIELDS: the scan kernel's instance and the post-pass
+        behind it; after a fall-back re-run, the re-run's."""
+        out = (C.c_int * 16)()
+        _check(self._lib.seeqdevScanLastPlan(self._h, out))
+        return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
 
     def last_packed_quad(self):
         """True when the last packed run walked the quad table (four bases per table step)."""

@@ -138,6 +138,8 @@ void seeqdevScanFree(seeqdev_scan_t *s)
 int seeqdevScanSetProfiling(seeqdev_scan_t *s, int on) { if (!s) { errno = EINVAL; return -1; } s->prof = on; return 0; }
 int seeqdevScanLastTimes(const seeqdev_scan_t *s, float ms[4]) { (void)s; ms[0] = ms[1] = ms[2] = ms[3] = 0.f; return 0; }
 int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *ms) { (void)s; *ms = 0.f; return 0; }
+/* (no planner behind the oracle: every scan reports the all-zero plan of a context that has not scanned) */
+int seeqdevScanLastPlan(const seeqdev_scan_t *s, int out[16]) { if (!s || !out) { errno = EINVAL; return -1; } memset(out, 0, 16 * sizeof out[0]); return 0; }
 
 /* The whole scan, as the device would deliver it: counts, ordered records, per record the offset of its line. */
 static void *job_main(void *arg)

@@ -434,6 +434,35 @@ extern "C" int harness_plan(const char *keys, int m, int tau, int options, int w
    return 0;
 }
 
+// The same for many scans of ONE pattern: the automata depend on (keys, m, tau) alone, so they are built once -- one PlanAutomata, filled on the
+// first row that asks -- as a device pattern builds them once for every scan that uses it.  rows[nrows][4]: options, want, flags, knob_kernel
+// (as harness_plan); avg_line[nrows]; out[nrows][16].  Returns the automata that were built (bit 0 k_stream's, bit 1 the pair automaton).
+extern "C" int harness_plan_many(const char *keys, int m, int tau, int nrows, const int *rows, const double *avg_line, int *out)
+{
+   PlanAutomata au;
+   std::memset(&au, 0, sizeof au);
+   plan_ctx ctx = {keys, m, tau};
+   for (int r = 0; r < nrows; r++) {
+      const int *row = rows + 4 * r;
+      const int flags = row[2];
+      ScanKnobs kn;
+      std::memset(&kn, 0, sizeof kn);
+      kn.kernel = row[3];
+      PlanIn in;
+      std::memset(&in, 0, sizeof in);
+      in.wlen = m; in.tau = tau; in.options = row[0]; in.want = row[1]; in.avg_line = avg_line[r];
+      in.force_ll = flags & 1; in.no_stream = (flags >> 1) & 1; in.no_stream_nd = (flags >> 2) & 1; in.no_window = (flags >> 3) & 1;
+      in.sample_dirty = (flags >> 4) & 1; in.multi_active = (flags >> 5) & 1;
+      in.seg_bytes = (size_t)0xF0000000u;
+      in.kn = &kn;
+      const ScanPlan p = seeq_plan_scan(in, au, plan_ensure_host, &ctx);
+      const int v[16] = {p.rc, p.path, p.fw, p.use_stream, p.use_pair, p.use_myers, p.filter, p.stream_ll, p.stream_sub, p.stream_wu, p.verify, p.order2,
+                         p.leaders, p.window_ok, p.ll_restart ? 2 : (p.ll_filter ? 1 : 0), (int)p.skip_back};
+      for (int i = 0; i < 16; i++) out[16 * r + i] = v[i];
+   }
+   return (au.sdfa_state != 0 ? 1 : 0) | (au.pair_state != 0 ? 2 : 0);
+}
+
 // ---- the owner of a scan context's buffers (seeq_amd/csrc/seeq_workspace.h): the same code seeqdev_scan embeds, over FAKE hooks --
 //      malloc-backed, every live block kept in a table (a release of a block that is not live, or of the wrong kind, is counted), the
 //      N-th request refused on demand.  harness_ws_script runs the call pattern of a context: first growths of five capacity groups

@@ -83,6 +83,11 @@ def test_context_state_getters_without_a_context(capi):
     C.set_errno(0)
     assert L.seeqdevScanFallback(None, C.byref(bits), C.byref(left)) == -1
     assert C.get_errno() == errno.EINVAL and (bits.value, left.value) == (7, 7)
+    # seeqdevScanLastPlan: the same -- EINVAL without a context or without somewhere to write, the sixteen numbers untouched
+    plan = (C.c_int * 16)(*([7] * 16))
+    C.set_errno(0)
+    assert L.seeqdevScanLastPlan(None, plan) == -1
+    assert C.get_errno() == errno.EINVAL and list(plan) == [7] * 16
 
 
 def test_seeqopen_errors(capi):
