@@ -66,10 +66,8 @@ static int demux_finish(seeqdev_scan *s, uint32_t nkeys, int npat, const DemuxSr
             hipLaunchKernelGGL(k_demux_emit, dim3((nmax + DEMUX_WG - 1) / DEMUX_WG, (unsigned)npat), dim3(DEMUX_WG), 0, st, *src,
                                (const uint32_t *)s->dm_key, (const uint32_t *)s->dm_aux, nkeys, s->dm_out, (uint32_t)s->cap_dm_out, s->d_dmcnt);
       }
-      HIP_TRY(hipGetLastError(), EIO);
    }
-   HIP_TRY(hipMemcpyAsync(s->h_dmcnt, s->d_dmcnt, sizeof(DemuxCnt), hipMemcpyDeviceToHost, st), EIO);
-   HIP_TRY(hipStreamSynchronize(st), EIO);
+   if (counters_fetch(s, s->h_dmcnt, s->d_dmcnt, sizeof(DemuxCnt))) return -1;
    const DemuxCnt &h = *s->h_dmcnt;
    if (h.bad || h.nassigned > s->cap_dm_out || (stage && h.slot != h.nassigned)) {
       snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the demultiplexer (flags %u, %u assigned, %u staged)", h.bad, h.nassigned, h.slot);
@@ -155,14 +153,8 @@ static int demux_fastq(seeqdev_scan *s)
    if (n) {
       if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
       if (reserve_impl(s, 0, 0, 0, n)) return -1;
-      if (fastq_launch(s, s->dm_out, nullptr, (uint32_t)n, true)) return -1;
-      HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-      const FastqCnt &f = *s->h_fqcnt;
-      if (f.bad || f.kept > n) {
-         snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the FASTQ filter (flags %u, %u of %zu kept)", f.bad, f.kept, n);
-         errno = EIO;
-         return -1;
-      }
+      FastqCnt f;
+      if (fastq_filter(s, s->dm_out, nullptr, (uint32_t)n, true, &f)) return -1;
       kept = f.kept;
       if (kept) {
          HIP_TRY(hipMemcpyAsync(s->dm_out, s->fq_rec, (size_t)kept * sizeof(uint4), hipMemcpyDeviceToDevice, s->stream), EIO);
@@ -223,13 +215,7 @@ extern "C" const seeqdev_demux_t *seeqdevScanDemuxDevice(const seeqdev_scan_t *s
 
 extern "C" int seeqdevScanCopyDemux(seeqdev_scan_t *s, seeqdev_demux_t *host_out, size_t first, size_t n)
 {
-   seeqerr = 0;
-   if (!s || (!host_out && n) || first > s->dm_nrec || n > s->dm_nrec - first) { errno = EINVAL; return -1; }
-   if (n == 0) return 0;
-   if (use_device(s->device)) return -1;
-   HIP_TRY(hipMemcpyAsync(host_out, s->dm_out + first, n * sizeof(seeqdev_demux_t), hipMemcpyDeviceToHost, s->stream), EIO);
-   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-   return 0;
+   return copy_out(s, host_out, s ? s->dm_out : NULL, sizeof(seeqdev_demux_t), s ? s->dm_nrec : 0, first, n);
 }
 
 #endif

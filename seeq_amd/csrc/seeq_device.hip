@@ -106,6 +106,7 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_packed.h"
 #include "seeq_multi.h"
 #include "seeq_demux.h"
+#include "seeq_tiles.h"
 #include "seeq_fastq.h"
 #include "seeq_strand.h"
 #include "seeq_insert.h"
@@ -411,6 +412,35 @@ static MultiPlan *multi_plan_for(MultiPlan **slot, const seeqdev_pattern_t *cons
 
 struct OccMemo { const void *fn; size_t lds; int per_cu; };
 
+/* Two events around a stretch of a stream's work, for a context that profiles: every call is a no-op unless `on` (the context's profiling
+   switch); the events are made on first use and go with the context (seeqdevScanFree). */
+struct EventPair {
+   hipEvent_t ev[2];
+   bool       made;
+   float      ms;                 /* what the last read() found; 0: nothing timed */
+   int begin(bool on, hipStream_t st)
+   {
+      if (!on) return 0;
+      if (!made) {
+         HIP_TRY(hipEventCreate(&ev[0]), EIO);
+         HIP_TRY(hipEventCreate(&ev[1]), EIO);
+         made = true;
+      }
+      HIP_TRY(hipEventRecord(ev[0], st), EIO);
+      return 0;
+   }
+   int end(bool on, hipStream_t st)
+   {
+      if (on) HIP_TRY(hipEventRecord(ev[1], st), EIO);
+      return 0;
+   }
+   void read(bool on)             /* (behind a synchronise) */
+   {
+      ms = 0.f;
+      if (on && made) (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+   }
+};
+
 /* Packed runs (seeq_packed.h), reads per segment: 64 Mi (16 Mi until the quad walk: the per-segment launches behind the walk -- the scan of the
    candidate counts, the list, k_nh_top, k_emit1 -- are latency-bound and cost as much for a quarter of the reads: 100 M reads, 2.28 ms per step
    in six segments, 2.11 in three, 2.07 in two; 8 bytes of workspace per read of a segment); SEEQ_PACKED_SEG_READS sets another size (tests) */
@@ -420,9 +450,7 @@ struct seeqdev_scan {
    hipStream_t stream;
    bool        own_stream;
    int         device;            /* the HIP device this context (its stream, its workspace) lives on */
-   hipEvent_t  ev_h2d[2];         /* profiling: around the H2D copy of seeqdevScanHostBegin */
-   bool        have_h2d_ev;
-   float       h2d_ms;            /* ... of the last fetched scan */
+   EventPair   tm_h2d;            /* profiling: around the H2D copy of seeqdevScanHostBegin; .ms: of the last fetched scan */
    float      *launch_ms; size_t cap_launch_ms;      /* per forward-scan launch of the last fetched scan (profiling) */
    unsigned long long *clk_probe;  /* page-locked, 4 words per segment: the scan kernel's own clock readings (profiling; k_pair) */
    size_t      cap_clk_probe;
@@ -500,13 +528,13 @@ struct seeqdev_scan {
    DemuxCnt *d_dmcnt, *h_dmcnt;                           /* h_ pinned */
    size_t    dm_nrec;                                     /* records of the last demux */
    uint64_t  dm_nlines;                                   /* its counted lines */
-   /* the first scan's records and offsets of a call that scans twice, aside on the device while the second scan runs (side_keep, seeq_strand_host.h:
+   /* the first scan's records and offsets of a call that scans twice, aside on the device while the second scan runs (side_keep:
       the plus strand of seeqdevScanRunStrands, the right flank of seeqdevScanRunInserts) */
    seeqdev_hit_t *side_rec; uint64_t *side_off; size_t cap_side;
    /* seeqdevScanRunStrands (seeq_strand.h): allocated by the first both-strands call */
    uint4    *st_mrg; uint64_t *st_mrg_off; uint32_t *st_bsum; size_t cap_st_mrg;      /* the merged records and offsets, the reduction's per-tile sums */
    StrandCnt *d_stcnt, *h_stcnt;                          /* h_ pinned */
-   hipEvent_t ev_st[2]; bool have_st_ev; float st_merge_ms;      /* profiling: around the merge's launches and copies (the FASTQ filter not included) */
+   EventPair tm_st;                                       /* profiling: around the merge's launches and copies (the FASTQ filter not included) */
    /* seeqdevScanRunInserts (seeq_insert.h): allocated by the first inserts call; the result (ins_rec, ins_off, ins_pos) is valid until the next one */
    uint4    *ins_jn; uint32_t *ins_bsum; uint64_t *ins_bbytes; size_t cap_ins_jn;      /* the joined records (one per left record), the reduction's per-tile sums */
    uint4    *ins_rec; uint64_t *ins_off, *ins_pos; size_t cap_ins;      /* the insert records, their line offsets, their byte positions in the insert text */
@@ -514,14 +542,14 @@ struct seeqdev_scan {
    size_t    ins_n;                                       /* records of the last inserts call */
    uint64_t  ins_text_bytes;                              /* bytes of its insert text */
    bool      ins_staged; size_t ins_staged_nbytes;        /* it scanned the context's staged text (seeqdevScanHostInserts), and d_text still holds it */
-   hipEvent_t ev_ins[2]; bool have_ins_ev; float ins_join_ms;      /* profiling: around the join's launches */
+   EventPair tm_ins;                                      /* profiling: around the join's launches */
    bool      ins_done;                                    /* an inserts call has completed: ins_n records (none included) are a result */
    /* seeqdevScanTally (seeq_tally.h): allocated by the first tally; the table (tl_tab, tl_n) is valid until the next one */
    uint64_t *tl_key0, *tl_key1; uint32_t *tl_mat, *tl_sum; uint4 *tl_stat; size_t cap_tl;      /* per span: the two key arrays; per tile: the digit matrix, the sums, the pack's numbers */
    seeqdev_tally_t *tl_tab; size_t cap_tl_tab;            /* the table: one entry per distinct key */
    TallyCnt *d_tlcnt, *h_tlcnt;                           /* h_ pinned */
    size_t    tl_n;                                        /* entries of the last tally's table */
-   hipEvent_t ev_tl[2]; bool have_tl_ev; float tl_ms;     /* profiling: around the tally's launches and counter copies */
+   EventPair tm_tl;                                       /* profiling: around the tally's launches and counter copies */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -641,10 +669,8 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
 {
    if (!s) return;
    (void)use_device(s->device);
-   if (s->have_h2d_ev) { (void)hipEventDestroy(s->ev_h2d[0]); (void)hipEventDestroy(s->ev_h2d[1]); }
-   if (s->have_st_ev) { (void)hipEventDestroy(s->ev_st[0]); (void)hipEventDestroy(s->ev_st[1]); }
-   if (s->have_ins_ev) { (void)hipEventDestroy(s->ev_ins[0]); (void)hipEventDestroy(s->ev_ins[1]); }
-   if (s->have_tl_ev) { (void)hipEventDestroy(s->ev_tl[0]); (void)hipEventDestroy(s->ev_tl[1]); }
+   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl})
+      if (t->made) { (void)hipEventDestroy(t->ev[0]); (void)hipEventDestroy(t->ev[1]); }
    (void)hipStreamSynchronize(s->stream);
    ws_free_all(&s->ws);
    multi_plan_free(s->mplan);
@@ -663,7 +689,7 @@ static int ensure_scan_ws(seeqdev_scan *s, size_t nblocks)
 }
 
 /* the filter's per-tile sums for n records (seeq_fastq.h: kept and opened per tile) */
-static size_t fastq_bsum_words(size_t n) { return 2 * (n / SEEQ_FASTQ_TILE + 2); }
+static size_t fastq_bsum_words(size_t n) { return 2 * (n / SEEQ_TILE + 2); }
 
 static int reserve_impl(seeqdev_scan *s, size_t max_bytes, size_t max_lines, size_t max_hitlines, size_t max_records)
 {
@@ -1485,17 +1511,50 @@ static int rerun_next(seeqdev_scan *s, int run, const Counters &u, const Counter
 
 static seeqdev_counts_t counts_of(const Counters &h) { return {h.lines, h.matchlines, h.hits, h.records, h.headers}; }
 
-/* SEEQDEV_FASTQ: the filter of seeq_fastq.h over the first n records of `in` (with their line offsets, or NULL) into the context's
-   scratch arrays, on its stream; the filter's counters follow to h_fqcnt.  Asynchronous; n > 0. */
-static int fastq_launch(seeqdev_scan *s, const void *in, const uint64_t *off_in, uint32_t n, bool demux)
+/* ---- plumbing of the entries behind a scan (the FASTQ filter, demux, both strands, inserts, the tally) ---- */
+/* a capacity as the kernels take it */
+static uint32_t cap_u32(size_t cap) { return (uint32_t)(cap < 0xFFFFFFFFull ? cap : 0xFFFFFFFFull); }
+
+/* Behind a run of launches: did they go out, and their counter block on its way to the (pinned) host copy. */
+static int counters_copy(seeqdev_scan *s, void *h, const void *d, size_t bytes)
+{
+   HIP_TRY(hipGetLastError(), EIO);
+   HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s->stream), EIO);
+   return 0;
+}
+
+/* ... and there: waits. */
+static int counters_fetch(seeqdev_scan *s, void *h, const void *d, size_t bytes)
+{
+   if (counters_copy(s, h, d, bytes)) return -1;
+   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
+   return 0;
+}
+
+/* Elements [first, first + n) of the `have` elements of `elem` bytes at the device address `base` -> host_out: the body of every
+   seeqdevScanCopy* entry.  Waits. */
+static int copy_out(seeqdev_scan *s, void *host_out, const void *base, size_t elem, size_t have, size_t first, size_t n)
+{
+   seeqerr = 0;
+   if (!s || (!host_out && n) || first > have || n > have - first) { errno = EINVAL; return -1; }
+   if (n == 0) return 0;
+   if (use_device(s->device)) return -1;
+   HIP_TRY(hipMemcpyAsync(host_out, (const char *)base + first * elem, n * elem, hipMemcpyDeviceToHost, s->stream), EIO);
+   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
+   return 0;
+}
+
+/* SEEQDEV_FASTQ: the filter of seeq_fastq.h over the first n > 0 records of `in` (with their line offsets, or NULL) into the context's
+   scratch arrays fq_rec / fq_off; *cnt: its counters, checked (demux: the tallies per pattern, and no lines are counted).  Waits. */
+static int fastq_filter(seeqdev_scan *s, const void *in, const uint64_t *off_in, uint32_t n, bool demux, FastqCnt *cnt)
 {
    const hipStream_t st = s->stream;
    FastqArgs a;
    memset(&a, 0, sizeof a);
    a.in = (const uint4 *)in; a.off_in = off_in;
    a.out = (uint4 *)s->fq_rec; a.off_out = s->fq_off;
-   a.n = n; a.cap_out = (uint32_t)(s->cap_fq < 0xFFFFFFFFull ? s->cap_fq : 0xFFFFFFFFull);
-   a.nb = (uint32_t)(((uint64_t)n + SEEQ_FASTQ_TILE - 1) / SEEQ_FASTQ_TILE);
+   a.n = n; a.cap_out = cap_u32(s->cap_fq);
+   a.nb = (uint32_t)seeq_tiles_of(n);
    a.bsum = s->fq_bsum;
    a.cnt = s->d_fqcnt;
    if (!s->fq_rec || !s->d_fqcnt || n > s->cap_fq || fastq_bsum_words(s->cap_fq) < 2 * (size_t)a.nb) {
@@ -1504,12 +1563,32 @@ static int fastq_launch(seeqdev_scan *s, const void *in, const uint64_t *off_in,
       return -1;
    }
    HIP_TRY(hipMemsetAsync(s->d_fqcnt, 0, sizeof(FastqCnt), st), EIO);
-   if (demux) hipLaunchKernelGGL(k_fastq_reduce<true>, dim3(a.nb), dim3(SEEQ_FASTQ_WG), 0, st, a);
-   else hipLaunchKernelGGL(k_fastq_reduce<false>, dim3(a.nb), dim3(SEEQ_FASTQ_WG), 0, st, a);
-   hipLaunchKernelGGL(k_fastq_top, dim3(1), dim3(SEEQ_FASTQ_WG), 0, st, a);
-   hipLaunchKernelGGL(k_fastq_apply, dim3(a.nb), dim3(SEEQ_FASTQ_WG), 0, st, a);
-   HIP_TRY(hipGetLastError(), EIO);
-   HIP_TRY(hipMemcpyAsync(s->h_fqcnt, s->d_fqcnt, sizeof(FastqCnt), hipMemcpyDeviceToHost, st), EIO);
+   if (demux) hipLaunchKernelGGL(k_fastq_reduce<true>, dim3(a.nb), dim3(SEEQ_TILE_WG), 0, st, a);
+   else hipLaunchKernelGGL(k_fastq_reduce<false>, dim3(a.nb), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_fastq_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_fastq_apply, dim3(a.nb), dim3(SEEQ_TILE_WG), 0, st, a);
+   if (counters_fetch(s, s->h_fqcnt, s->d_fqcnt, sizeof(FastqCnt))) return -1;
+   *cnt = *s->h_fqcnt;
+   if (cnt->bad || cnt->kept > n || cnt->opened > cnt->kept) {
+      snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the FASTQ filter (flags %u, %u of %u kept, %u lines)", cnt->bad, cnt->kept, n, cnt->opened);
+      errno = EIO;
+      return -1;
+   }
+   return 0;
+}
+
+/* The filter over the context's first n > 0 records; the filtered arrays become the context's records, and what was scanned into is the
+   next filter's scratch (no copy back). */
+static int fastq_filter_swap(seeqdev_scan *s, uint32_t n, FastqCnt *cnt)
+{
+   if (s->cap_fq != s->cap_records) {
+      snprintf(g_last_error, sizeof g_last_error, "FASTQ filter: scratch for %zu records, record workspace for %zu", s->cap_fq, s->cap_records);
+      errno = EIO;
+      return -1;
+   }
+   if (fastq_filter(s, s->records, s->rec_off, n, false, cnt)) return -1;
+   seeqdev_hit_t *r = s->records; s->records = s->fq_rec; s->fq_rec = r;
+   uint64_t *o = s->rec_off; s->rec_off = s->fq_off; s->fq_off = o;
    return 0;
 }
 
@@ -1521,31 +1600,13 @@ static int fastq_finish(seeqdev_scan *s, const Counters &h)
       errno = E2BIG;
       return -1;
    }
-   const uint32_t n = (uint32_t)h.records;
-   uint32_t kept = 0, opened = 0;
-   if (n) {
-      if (s->cap_fq != s->cap_records) {
-         snprintf(g_last_error, sizeof g_last_error, "FASTQ filter: scratch for %zu records, record workspace for %zu", s->cap_fq, s->cap_records);
-         errno = EIO;
-         return -1;
-      }
-      if (fastq_launch(s, s->records, s->rec_off, n, false)) return -1;
-      HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-      const FastqCnt &f = *s->h_fqcnt;
-      if (f.bad || f.kept > n || f.opened > f.kept) {
-         snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the FASTQ filter (flags %u, %u of %u kept, %u lines)", f.bad, f.kept, n, f.opened);
-         errno = EIO;
-         return -1;
-      }
-      kept = f.kept; opened = f.opened;
-      /* the filtered arrays become the context's records; what was scanned into is the next filter's scratch (no copy back) */
-      seeqdev_hit_t *r = s->records; s->records = s->fq_rec; s->fq_rec = r;
-      uint64_t *o = s->rec_off; s->rec_off = s->fq_off; s->fq_off = o;
-   }
+   FastqCnt f;
+   f.kept = f.opened = 0;
+   if (h.records && fastq_filter_swap(s, (uint32_t)h.records, &f)) return -1;
    s->counts.nlines = fastq_nlines(h.lines);
-   s->counts.nmatchlines = opened;
-   s->counts.nhits = s->fq_want == SEEQDEV_WANT_COUNTLINES ? opened : kept;
-   s->counts.nrecords = s->fq_want == SEEQDEV_WANT_RECORDS ? kept : 0;
+   s->counts.nmatchlines = f.opened;
+   s->counts.nhits = s->fq_want == SEEQDEV_WANT_COUNTLINES ? f.opened : f.kept;
+   s->counts.nrecords = s->fq_want == SEEQDEV_WANT_RECORDS ? f.kept : 0;
    s->counts.nheaders = 0;
    return 0;
 }
@@ -1592,8 +1653,7 @@ extern "C" int seeqdevScanFetch(seeqdev_scan_t *s, seeqdev_counts_t *counts)
             if (nn) s->clk_mhz = (float)(sum / (double)nn);
          }
          if (s->prof_segs) s->fwd_ms_avg = s->acc_ms[1] / (float)s->prof_segs;
-         s->h2d_ms = 0.f;
-         if (s->prof && s->have_h2d_ev) (void)hipEventElapsedTime(&s->h2d_ms, s->ev_h2d[0], s->ev_h2d[1]);
+         s->tm_h2d.read(s->prof);
          return 0;
       }
       if (dispatch_run(s)) return -1;
@@ -1604,15 +1664,7 @@ extern "C" const seeqdev_hit_t *seeqdevScanRecordsDevice(const seeqdev_scan_t *s
 
 extern "C" int seeqdevScanCopyRecords(seeqdev_scan_t *s, seeqdev_hit_t *host_out, size_t first, size_t n)
 {
-   seeqerr = 0;
-   if (!s || (!host_out && n)) { errno = EINVAL; return -1; }
-   if (first + n > s->counts.nrecords) { errno = EINVAL; return -1; }
-   if (n == 0) return 0;
-   if (use_device(s->device)) return -1;
-   HIP_TRY(hipMemcpyAsync(host_out, s->records + first, n * sizeof(seeqdev_hit_t), hipMemcpyDeviceToHost, s->stream),
-           EIO);
-   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-   return 0;
+   return copy_out(s, host_out, s ? s->records : NULL, sizeof(seeqdev_hit_t), s ? (size_t)s->counts.nrecords : 0, first, n);
 }
 
 /* A packed read batch resident in HBM (seeq_amd.h: seeqdev_packed_t, seeq_packed.h): asynchronous, seeqdevScanFetch waits. */
@@ -1705,14 +1757,7 @@ extern "C" long seeqdevPackReads(const char *text, size_t nbytes, uint32_t read_
 
 extern "C" int seeqdevScanCopyOffsets(seeqdev_scan_t *s, uint64_t *host_out, size_t first, size_t n)
 {
-   seeqerr = 0;
-   if (!s || (!host_out && n)) { errno = EINVAL; return -1; }
-   if (first + n > s->counts.nrecords) { errno = EINVAL; return -1; }
-   if (n == 0) return 0;
-   if (use_device(s->device)) return -1;
-   HIP_TRY(hipMemcpyAsync(host_out, s->rec_off + first, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream), EIO);
-   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-   return 0;
+   return copy_out(s, host_out, s ? s->rec_off : NULL, sizeof(uint64_t), s ? (size_t)s->counts.nrecords : 0, first, n);
 }
 
 /* The context's staging buffer holds nbytes (grown with a quarter to spare) */
@@ -1728,11 +1773,38 @@ static int text_ensure(seeqdev_scan *s, size_t nbytes)
 static int text_upload(seeqdev_scan *s, const char *host_text, size_t nbytes, bool timed)
 {
    if (text_ensure(s, nbytes)) return -1;
-   if (timed) HIP_TRY(hipEventRecord(s->ev_h2d[0], s->stream), EIO);
+   if (s->tm_h2d.begin(timed, s->stream)) return -1;
    if (nbytes) HIP_TRY(hipMemcpyAsync(s->d_text, host_text, nbytes, hipMemcpyHostToDevice, s->stream), EIO);
-   if (timed) HIP_TRY(hipEventRecord(s->ev_h2d[1], s->stream), EIO);
+   if (s->tm_h2d.end(timed, s->stream)) return -1;
    s->avg_text = NULL;
-   s->ins_staged = false;                                  /* (seeqdevScanInsertText: the staged text of the last inserts call is gone) */
+   s->ins_staged = false;                                  /* (staged_text: the staged text of the last inserts call is gone) */
+   return 0;
+}
+
+/* An entry that was given no text (*d_text NULL) works on the staged text of the last inserts call (seeqdevScanHostInserts), or refuses
+   under its own name `who`. */
+static int staged_text(seeqdev_scan *s, const char *who, const void **d_text, size_t *nbytes)
+{
+   if (*d_text) return 0;
+   if (!s->ins_staged) {
+      snprintf(g_last_error, sizeof g_last_error, "%s: the context holds no staged text of an inserts call", who);
+      errno = EINVAL;
+      return -1;
+   }
+   *d_text = s->d_text;
+   *nbytes = s->ins_staged_nbytes;
+   return 0;
+}
+
+/* The first n records of the scan just fetched, with their offsets, copied aside on the device (16 + 8 bytes per record) before the call's
+   next scan overwrites them: the one owner of the side copy (the both-strands call's plus records, the inserts call's right records).  Waits. */
+static int side_keep(seeqdev_scan *s, size_t n)
+{
+   if (!n) return 0;
+   if (ws_grow(&s->ws, &s->cap_side, n, {{s->side_rec, n * sizeof(seeqdev_hit_t)}, {s->side_off, n * sizeof(uint64_t)}})) return -1;
+   HIP_TRY(hipMemcpyAsync(s->side_rec, s->records, n * sizeof(seeqdev_hit_t), hipMemcpyDeviceToDevice, s->stream), EIO);
+   HIP_TRY(hipMemcpyAsync(s->side_off, s->rec_off, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s->stream), EIO);
+   HIP_TRY(hipStreamSynchronize(s->stream), EIO);            /* the next scan may reallocate the records the copies read */
    return 0;
 }
 
@@ -1742,11 +1814,6 @@ extern "C" int seeqdevScanHostBegin(seeqdev_scan_t *s, const seeqdev_pattern_t *
    seeqerr = 0;
    if (!s || !pat || (!host_text && nbytes)) { errno = EINVAL; return -1; }
    if (use_device(s->device)) return -1;
-   if (s->prof && !s->have_h2d_ev) {
-      HIP_TRY(hipEventCreate(&s->ev_h2d[0]), EIO);
-      HIP_TRY(hipEventCreate(&s->ev_h2d[1]), EIO);
-      s->have_h2d_ev = true;
-   }
    if (text_upload(s, host_text, nbytes, s->prof)) return -1;
    /* the line-length sample (kernel selection) comes from the host copy: no round trip, nothing stale */
    if (s->line_hint <= 0 && !(options & SEEQDEV_SINGLELINE) && nbytes) {
@@ -1776,7 +1843,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {
    if (!s || !h2d_ms) { errno = EINVAL; return -1; }
-   *h2d_ms = s->h2d_ms;
+   *h2d_ms = s->tm_h2d.ms;
    return 0;
 }
 

@@ -19,13 +19,14 @@
  *                        prefix of end - start + 1.  Output byte b belongs to the last record whose pos is <= b (positions increase
  *                        strictly: an empty insert still has its newline).
  *
- *   k_insert_join     one thread per left record, tiles of SEEQ_INSERT_TILE (a thread owns records tile + k * 256 + tid): the search
- *                     and the walk, one 16-byte store of the insert record AT THE LEFT RECORD'S OWN INDEX; line number 0 (free: lines
- *                     are 1-based) when nothing is admissible, and then `start` tells whether the line has a right record at all.
- *   k_insert_reduce   per tile of the joined array: records kept (line != 0), lines with both flanks, the kept records' text bytes.
+ *   k_insert_join     one thread per left record, in the tiles of seeq_tiles.h: the search and the walk, one 16-byte store of the insert
+ *                     record AT THE LEFT RECORD'S OWN INDEX; line number 0 (free: lines are 1-based) when nothing is admissible, and
+ *                     then `start` tells whether the line has a right record at all.
+ *   and over the joined array the reduce / top / apply of seeq_tiles.h:
+ *   k_insert_reduce   per tile: records kept (line != 0), lines with both flanks; the kept records' text bytes (64 bits, a sum of its own).
  *   k_insert_top      one workgroup: exclusive scans of the tiles' kept counts (32 bits) and text bytes (64 bits) in place; the totals.
- *   k_insert_apply    the ordered compaction that drops line 0 (as k_strand_apply): record, line offset, and the record's byte position
- *                     in the insert text.
+ *   k_insert_apply    the ordered compaction that drops line 0: record, line offset, and the record's byte position in the insert
+ *                     text (the exclusive prefix of the text bytes, carried with the ranks).
  *   k_insert_text     the gather, balanced by OUTPUT BYTES: a thread owns SEEQ_INSERT_RUN consecutive output bytes, finds the record of
  *                     its first byte by one binary search over the positions and walks forward; one aligned 16-byte store where the
  *                     output buffer allows.  It checks offset + end <= nbytes against the text it was given (`bad` otherwise).
@@ -43,10 +44,10 @@
 
 #include "seeq_strand.h"                                    /* strand_rec_t, strand_key, strand_count_below, strand_partner */
 
-#define SEEQ_INSERT_WG    256                               /* threads of a workgroup (4 waves) */
-#define SEEQ_INSERT_ITEMS 4                                 /* records per thread */
-#define SEEQ_INSERT_TILE  1024                              /* records per workgroup = SEEQ_INSERT_WG * SEEQ_INSERT_ITEMS */
-#define SEEQ_INSERT_RUN   16                                /* output bytes per thread of k_insert_text */
+#define SEEQ_INSERT_WG    SEEQ_TILE_WG                      /* (the host driver prints the shape under the join's names) */
+#define SEEQ_INSERT_ITEMS SEEQ_TILE_ITEMS
+#define SEEQ_INSERT_TILE  SEEQ_TILE
+#define SEEQ_INSERT_RUN   16                               /* output bytes per thread of k_insert_text */
 
 #define SEEQ_INSERT_FIRST 0                                 /* = SQ_FIRST, SQ_BEST (libseeq.h) */
 #define SEEQ_INSERT_BEST  1
@@ -147,7 +148,7 @@ SEEQ_ST_HD int insert_text_fill(const strand_rec_t *rec, const uint64_t *off, co
 
 #if defined(__HIPCC__)
 
-static_assert(SEEQ_INSERT_TILE == SEEQ_INSERT_WG * SEEQ_INSERT_ITEMS && SEEQ_INSERT_WG == SEEQ_WG && SEEQ_INSERT_RUN == 16, "insert tile / workgroup / run");
+static_assert(SEEQ_INSERT_RUN == 16, "k_insert_text stores a run as one uint4");
 
 struct InsertCnt {
    uint64_t bytes;                    /* the insert text: sum over the kept records of end - start + 1 */
@@ -187,50 +188,11 @@ struct InsertTextArgs {
    InsertCnt      *cnt;
 };
 
-__device__ __forceinline__ uint64_t insert_shfl_up64(uint64_t v, int d)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_insert_join(InsertArgs a)
 {
-   const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, 64);
-   return ((uint64_t)hi << 32) | lo;
-}
-
-/* inclusive scan over the wave's 64 lanes */
-__device__ __forceinline__ uint64_t insert_wave_incl_scan64(uint64_t v)
-{
-   const int lane = threadIdx.x & 63;
-   uint64_t x = v;
 #pragma unroll
-   for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t y = insert_shfl_up64(x, d);
-      if (lane >= d) x += y;
-   }
-   return x;
-}
-
-/* block_excl_scan (seeq_scan_common.h) for 64-bit values */
-__device__ __forceinline__ uint64_t insert_block_excl_scan64(uint64_t v, uint64_t *total, uint64_t *s_wave /* >= 4 */)
-{
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const uint64_t x = insert_wave_incl_scan64(v);
-   if (lane == 63) s_wave[wave] = x;
-   __syncthreads();
-   uint64_t base = 0, tot = 0;
-#pragma unroll
-   for (int w = 0; w < SEEQ_INSERT_WG / 64; w++) {
-      const uint64_t s = s_wave[w];
-      if (w < wave) base += s;
-      tot += s;
-   }
-   __syncthreads();
-   *total = tot;
-   return base + x - v;
-}
-
-__global__ __launch_bounds__(SEEQ_INSERT_WG) void k_insert_join(InsertArgs a)
-{
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_INSERT_TILE;
-#pragma unroll
-   for (int k = 0; k < SEEQ_INSERT_ITEMS; k++) {
-      const uint64_t t = base + (uint64_t)k * SEEQ_INSERT_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t t = tile_index(k);
       if (t >= a.nl) continue;
       const uint4 r = insert_join_one(a.mode, a.left[t], a.right, a.nr, a.min_len, a.max_len);
       if (t < a.cap_jn) a.jn[t] = r;
@@ -238,78 +200,55 @@ __global__ __launch_bounds__(SEEQ_INSERT_WG) void k_insert_join(InsertArgs a)
    }
 }
 
-__global__ __launch_bounds__(SEEQ_INSERT_WG) void k_insert_reduce(InsertArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_insert_reduce(InsertArgs a)
 {
-   __shared__ uint32_t s_kept[SEEQ_INSERT_WG / 64], s_both[SEEQ_INSERT_WG / 64];
-   __shared__ uint64_t s_bytes[SEEQ_INSERT_WG / 64];
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_INSERT_TILE;
-   uint32_t kept = 0, both = 0;                             /* wave-uniform */
+   __shared__ uint32_t s_sum[2][SEEQ_TILE_WAVES];
+   __shared__ uint64_t s_bytes[SEEQ_TILE_WAVES];
+   uint32_t sum[2] = {0u, 0u};                              /* kept, both: wave-uniform */
    uint64_t bytes = 0;                                      /* this lane's */
 #pragma unroll
-   for (int k = 0; k < SEEQ_INSERT_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_INSERT_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = tile_index(k);
       uint4 r = make_uint4(0u, 0u, 0u, 0u);
       if (i < a.nl) r = a.jn[i];
       const bool keep = r.x != 0u;
-      kept += (uint32_t)__popcll(__ballot(keep));
-      both += (uint32_t)__popcll(__ballot(keep || r.y != 0u));      /* (no record: y is the line's "has a right record") */
+      sum[0] += (uint32_t)__popcll(__ballot(keep));
+      sum[1] += (uint32_t)__popcll(__ballot(keep || r.y != 0u));    /* (no record: y is the line's "has a right record") */
       if (keep) bytes += insert_text_len(r);
    }
-   bytes = insert_wave_incl_scan64(bytes);                  /* lane 63: the wave's sum */
-   if (lane == 63) { s_kept[wave] = kept; s_both[wave] = both; s_bytes[wave] = bytes; }
-   __syncthreads();
+   bytes = wave_incl_scan_u64(bytes);                       /* the publishing lane, the last one: the wave's sum */
+   if (tile_publishes()) s_bytes[threadIdx.x >> 6] = bytes;
+   tile_sums(sum, s_sum, a.bsum, a.nt);                     /* (its barrier is s_bytes' too) */
    if (threadIdx.x == 0) {
-      kept = both = 0;
       bytes = 0;
-      for (int w = 0; w < SEEQ_INSERT_WG / 64; w++) { kept += s_kept[w]; both += s_both[w]; bytes += s_bytes[w]; }
-      a.bsum[blockIdx.x] = kept;
-      a.bsum[a.nt + blockIdx.x] = both;
+      for (int w = 0; w < SEEQ_TILE_WAVES; w++) bytes += s_bytes[w];
       a.bbytes[blockIdx.x] = bytes;
    }
 }
 
 /* One workgroup: bsum[0 .. nt) and bbytes[0 .. nt) -> their exclusive prefixes, in place; the totals (kept, both: at most nl). */
-__global__ __launch_bounds__(SEEQ_INSERT_WG) void k_insert_top(InsertArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_insert_top(InsertArgs a)
 {
-   __shared__ uint32_t s_wave[SEEQ_INSERT_WG / 64];
-   __shared__ uint64_t s_wave64[SEEQ_INSERT_WG / 64];
-   uint32_t running = 0, both = 0;
-   uint64_t running_bytes = 0;
-   for (uint32_t b0 = 0; b0 < a.nt; b0 += SEEQ_INSERT_WG) {
-      const uint32_t i = b0 + threadIdx.x;
-      const uint32_t v = i < a.nt ? a.bsum[i] : 0u;
-      const uint64_t vb = i < a.nt ? a.bbytes[i] : 0u;
-      uint32_t tot;
-      uint64_t tot_bytes;
-      const uint32_t ex = block_excl_scan(v, &tot, s_wave);
-      const uint64_t exb = insert_block_excl_scan64(vb, &tot_bytes, s_wave64);
-      if (i < a.nt) {
-         a.bsum[i] = running + ex;
-         a.bbytes[i] = running_bytes + exb;
-         both += a.bsum[a.nt + i];
-      }
-      running += tot;
-      running_bytes += tot_bytes;
-   }
-   uint32_t tot_both;
-   block_excl_scan(both, &tot_both, s_wave);
-   if (threadIdx.x == 0) { a.cnt->kept = running; a.cnt->both = tot_both; a.cnt->bytes = running_bytes; }
+   __shared__ uint32_t s_wave[SEEQ_TILE_WAVES];
+   __shared__ uint64_t s_wave64[SEEQ_TILE_WAVES];
+   uint32_t tot[2];
+   uint64_t tot_bytes[1];
+   tile_top(a.bsum, a.nt, s_wave, tot);
+   tile_top(a.bbytes, a.nt, s_wave64, tot_bytes);
+   if (threadIdx.x == 0) { a.cnt->kept = tot[0]; a.cnt->both = tot[1]; a.cnt->bytes = tot_bytes[0]; }
 }
 
-__global__ __launch_bounds__(SEEQ_INSERT_WG) void k_insert_apply(InsertArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_insert_apply(InsertArgs a)
 {
-   __shared__ uint32_t s_cnt[SEEQ_INSERT_ITEMS][SEEQ_INSERT_WG / 64];
-   __shared__ uint64_t s_bytes[SEEQ_INSERT_ITEMS][SEEQ_INSERT_WG / 64];
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_INSERT_TILE;
-   uint4 r[SEEQ_INSERT_ITEMS];
-   uint64_t off[SEEQ_INSERT_ITEMS];
-   uint32_t within[SEEQ_INSERT_ITEMS];                      /* kept records of the wave's round before this lane */
-   uint64_t bytes_within[SEEQ_INSERT_ITEMS];                /* their text bytes */
+   __shared__ uint32_t s_cnt[SEEQ_TILE_ITEMS][SEEQ_TILE_WAVES];
+   __shared__ uint64_t s_bytes[SEEQ_TILE_ITEMS][SEEQ_TILE_WAVES];
+   uint4 r[SEEQ_TILE_ITEMS];
+   uint64_t off[SEEQ_TILE_ITEMS];
+   uint32_t within[SEEQ_TILE_ITEMS];                        /* kept records of the wave's round before this lane */
+   uint64_t bytes_within[SEEQ_TILE_ITEMS];                  /* their text bytes */
 #pragma unroll
-   for (int k = 0; k < SEEQ_INSERT_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_INSERT_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = tile_index(k);
       r[k] = make_uint4(0u, 0u, 0u, 0u);
       off[k] = 0;
       if (i < a.nl) {
@@ -317,46 +256,30 @@ __global__ __launch_bounds__(SEEQ_INSERT_WG) void k_insert_apply(InsertArgs a)
          if (r[k].x != 0u) off[k] = a.left_off[i];
       }
       const bool keep = r[k].x != 0u;
-      const uint64_t b = __ballot(keep);
-      within[k] = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-      const uint64_t len = keep ? insert_text_len(r[k]) : 0u;
-      const uint64_t incl = insert_wave_incl_scan64(len);
-      bytes_within[k] = incl - len;
-      if (lane == 63) { s_cnt[k][wave] = (uint32_t)__popcll(b); s_bytes[k][wave] = incl; }
+      bytes_within[k] = tile_wave_offset(keep ? insert_text_len(r[k]) : 0u, s_bytes[k]);
+      within[k] = tile_wave_rank(keep, s_cnt[k]);           /* (behind the scan: 64 VGPRs, two fewer than before it, and 66 are a wave less per SIMD) */
    }
    __syncthreads();
    uint32_t rank0 = a.bsum[blockIdx.x];                     /* kept records before this tile, then before this round */
    uint64_t byte0 = a.bbytes[blockIdx.x];                   /* their text bytes */
 #pragma unroll
-   for (int k = 0; k < SEEQ_INSERT_ITEMS; k++) {
-      uint32_t before = 0, tot = 0;
-      uint64_t bytes_before = 0, tot_bytes = 0;
-#pragma unroll
-      for (int w = 0; w < SEEQ_INSERT_WG / 64; w++) {
-         const uint32_t c = s_cnt[k][w];
-         const uint64_t cb = s_bytes[k][w];
-         if (w < wave) { before += c; bytes_before += cb; }
-         tot += c;
-         tot_bytes += cb;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint32_t j = tile_place(rank0, within[k], s_cnt[k]);
+      const uint64_t pos = tile_place(byte0, bytes_within[k], s_bytes[k]);
+      if (r[k].x == 0u) continue;
+      if (j < a.cap_out) {
+         a.out[j] = r[k];
+         a.off_out[j] = off[k];
+         a.pos_out[j] = pos;
+      } else {
+         atomicOr(&a.cnt->bad, 1u);
       }
-      if (r[k].x != 0u) {
-         const uint32_t j = rank0 + before + within[k];
-         if (j < a.cap_out) {
-            a.out[j] = r[k];
-            a.off_out[j] = off[k];
-            a.pos_out[j] = byte0 + bytes_before + bytes_within[k];
-         } else {
-            atomicOr(&a.cnt->bad, 1u);
-         }
-      }
-      rank0 += tot;
-      byte0 += tot_bytes;
    }
 }
 
-__global__ __launch_bounds__(SEEQ_INSERT_WG) void k_insert_text(InsertTextArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_insert_text(InsertTextArgs a)
 {
-   const uint64_t b0 = ((uint64_t)blockIdx.x * SEEQ_INSERT_WG + threadIdx.x) * SEEQ_INSERT_RUN;
+   const uint64_t b0 = ((uint64_t)blockIdx.x * SEEQ_TILE_WG + threadIdx.x) * SEEQ_INSERT_RUN;
    if (b0 >= a.total) return;
    const int cnt = a.total - b0 < SEEQ_INSERT_RUN ? (int)(a.total - b0) : SEEQ_INSERT_RUN;
    uint32_t w[SEEQ_INSERT_RUN / 4];

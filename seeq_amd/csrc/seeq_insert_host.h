@@ -1,6 +1,6 @@
 /*
  * seeq_insert_host.h -- the host driver of the insert between two flanks (rule and kernels: seeq_insert.h): the right flank's scan under
- * SQ_ALL with its records kept aside (side_keep, seeq_strand_host.h), the left flank's scan under the call's mode, the join and the
+ * SQ_ALL with its records kept aside (side_keep), the left flank's scan under the call's mode, the join and the
  * compaction on the device, the gather of the insert text, and the seeqdevScan*Insert* entries.  Included by seeq_device.hip behind
  * seeq_strand_host.h.
  */
@@ -8,7 +8,7 @@
 #define SEEQ_INSERT_HOST_H_
 
 /* the reduction's per-tile sums for n left records (seeq_insert.h: kept and both per tile; text bytes per tile) */
-static size_t insert_tiles(size_t n) { return n / SEEQ_INSERT_TILE + 2; }
+static size_t insert_tiles(size_t n) { return n / SEEQ_TILE + 2; }
 
 /* Room for n joined records and their tiles' sums.  Nothing on the stream reads the old blocks: every inserts call ends synchronised. */
 static int inserts_ws_join(seeqdev_scan *s, size_t n)
@@ -48,8 +48,8 @@ static int inserts_join(seeqdev_scan *s, uint32_t nl, uint32_t nr, int mode, uin
    a.left = (const uint4 *)s->records; a.left_off = s->rec_off; a.nl = nl;
    a.right = (const uint4 *)s->side_rec; a.nr = nr;
    a.min_len = min_len; a.max_len = max_len; a.mode = mode;
-   a.jn = s->ins_jn; a.cap_jn = (uint32_t)(s->cap_ins_jn < 0xFFFFFFFFull ? s->cap_ins_jn : 0xFFFFFFFFull);
-   a.nt = (uint32_t)(((uint64_t)nl + SEEQ_INSERT_TILE - 1) / SEEQ_INSERT_TILE);
+   a.jn = s->ins_jn; a.cap_jn = cap_u32(s->cap_ins_jn);
+   a.nt = (uint32_t)seeq_tiles_of(nl);
    a.bsum = s->ins_bsum; a.bbytes = s->ins_bbytes;
    a.cnt = s->d_inscnt;
    if (insert_tiles(s->cap_ins_jn) < (size_t)a.nt || (size_t)nr > s->cap_side) {
@@ -57,19 +57,12 @@ static int inserts_join(seeqdev_scan *s, uint32_t nl, uint32_t nr, int mode, uin
       errno = EIO;
       return -1;
    }
-   if (s->prof && !s->have_ins_ev) {
-      HIP_TRY(hipEventCreate(&s->ev_ins[0]), EIO);
-      HIP_TRY(hipEventCreate(&s->ev_ins[1]), EIO);
-      s->have_ins_ev = true;
-   }
-   if (s->prof) HIP_TRY(hipEventRecord(s->ev_ins[0], st), EIO);
+   if (s->tm_ins.begin(s->prof, st)) return -1;
    HIP_TRY(hipMemsetAsync(s->d_inscnt, 0, sizeof(InsertCnt), st), EIO);
-   hipLaunchKernelGGL(k_insert_join, dim3(a.nt), dim3(SEEQ_INSERT_WG), 0, st, a);
-   hipLaunchKernelGGL(k_insert_reduce, dim3(a.nt), dim3(SEEQ_INSERT_WG), 0, st, a);
-   hipLaunchKernelGGL(k_insert_top, dim3(1), dim3(SEEQ_INSERT_WG), 0, st, a);
-   HIP_TRY(hipGetLastError(), EIO);
-   HIP_TRY(hipMemcpyAsync(s->h_inscnt, s->d_inscnt, sizeof(InsertCnt), hipMemcpyDeviceToHost, st), EIO);
-   HIP_TRY(hipStreamSynchronize(st), EIO);
+   hipLaunchKernelGGL(k_insert_join, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_insert_reduce, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_insert_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+   if (counters_fetch(s, s->h_inscnt, s->d_inscnt, sizeof(InsertCnt))) return -1;
    const InsertCnt h = *s->h_inscnt;
    if (h.bad || h.kept > h.both || h.both > nl || h.bytes < h.kept) {
       snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the insert join (flags %u, %u inserts, %u of %u lines with both flanks, %llu bytes)", h.bad,
@@ -80,14 +73,13 @@ static int inserts_join(seeqdev_scan *s, uint32_t nl, uint32_t nr, int mode, uin
    if (h.kept) {
       if (inserts_ws_result(s, h.kept)) return -1;
       a.out = s->ins_rec; a.off_out = s->ins_off; a.pos_out = s->ins_pos;
-      a.cap_out = (uint32_t)(s->cap_ins < 0xFFFFFFFFull ? s->cap_ins : 0xFFFFFFFFull);
-      hipLaunchKernelGGL(k_insert_apply, dim3(a.nt), dim3(SEEQ_INSERT_WG), 0, st, a);
-      HIP_TRY(hipGetLastError(), EIO);
-      HIP_TRY(hipMemcpyAsync(s->h_inscnt, s->d_inscnt, sizeof(InsertCnt), hipMemcpyDeviceToHost, st), EIO);
+      a.cap_out = cap_u32(s->cap_ins);
+      hipLaunchKernelGGL(k_insert_apply, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+      if (counters_copy(s, s->h_inscnt, s->d_inscnt, sizeof(InsertCnt))) return -1;
    }
-   if (s->prof) HIP_TRY(hipEventRecord(s->ev_ins[1], st), EIO);
+   if (s->tm_ins.end(s->prof, st)) return -1;
    HIP_TRY(hipStreamSynchronize(st), EIO);
-   if (s->prof) (void)hipEventElapsedTime(&s->ins_join_ms, s->ev_ins[0], s->ev_ins[1]);
+   s->tm_ins.read(s->prof);
    if (s->h_inscnt->bad) {
       snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the insert join (an index outside the output)");
       errno = EIO;
@@ -146,7 +138,7 @@ static int inserts_entry(seeqdev_scan_t *s, const seeqdev_pattern_t *left, const
    s->ins_text_bytes = 0;
    s->ins_staged = false;
    s->ins_done = false;
-   s->ins_join_ms = 0.f;
+   s->tm_ins.ms = 0.f;
    seeqdev_insert_counts_t c;
    const int rc = inserts_run(s, left, right, d_text, nbytes, options, min_len, max_len, &c);
    scan_forget(s);                                         /* (seeqdevScanFetch has nothing to fetch: the call is complete) */
@@ -183,26 +175,12 @@ extern "C" const seeqdev_insert_t *seeqdevScanInsertsDevice(const seeqdev_scan_t
 
 extern "C" int seeqdevScanCopyInserts(seeqdev_scan_t *s, seeqdev_insert_t *host_out, size_t first, size_t n)
 {
-   seeqerr = 0;
-   if (!s || (!host_out && n)) { errno = EINVAL; return -1; }
-   if (first > s->ins_n || n > s->ins_n - first) { errno = EINVAL; return -1; }
-   if (n == 0) return 0;
-   if (use_device(s->device)) return -1;
-   HIP_TRY(hipMemcpyAsync(host_out, s->ins_rec + first, n * sizeof(seeqdev_insert_t), hipMemcpyDeviceToHost, s->stream), EIO);
-   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-   return 0;
+   return copy_out(s, host_out, s ? s->ins_rec : NULL, sizeof(seeqdev_insert_t), s ? s->ins_n : 0, first, n);
 }
 
 extern "C" int seeqdevScanCopyInsertOffsets(seeqdev_scan_t *s, uint64_t *host_out, size_t first, size_t n)
 {
-   seeqerr = 0;
-   if (!s || (!host_out && n)) { errno = EINVAL; return -1; }
-   if (first > s->ins_n || n > s->ins_n - first) { errno = EINVAL; return -1; }
-   if (n == 0) return 0;
-   if (use_device(s->device)) return -1;
-   HIP_TRY(hipMemcpyAsync(host_out, s->ins_off + first, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream), EIO);
-   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-   return 0;
+   return copy_out(s, host_out, s ? s->ins_off : NULL, sizeof(uint64_t), s ? s->ins_n : 0, first, n);
 }
 
 extern "C" int seeqdevScanInsertText(seeqdev_scan_t *s, const void *d_text, size_t nbytes, void *d_out, size_t out_cap, uint64_t *out_bytes)
@@ -214,17 +192,9 @@ extern "C" int seeqdevScanInsertText(seeqdev_scan_t *s, const void *d_text, size
    if (!d_out && out_cap == 0) return 0;                   /* the size query */
    if ((uint64_t)out_cap < total) { errno = ERANGE; return -1; }
    if (!d_out) { errno = EINVAL; return -1; }
-   if (!d_text) {
-      if (!s->ins_staged) {
-         snprintf(g_last_error, sizeof g_last_error, "insert text: the context holds no staged text of an inserts call");
-         errno = EINVAL;
-         return -1;
-      }
-      d_text = s->d_text;
-      nbytes = s->ins_staged_nbytes;
-   }
+   if (staged_text(s, "insert text", &d_text, &nbytes)) return -1;
    if (total == 0) return 0;
-   const uint64_t blocks = (total + (uint64_t)SEEQ_INSERT_RUN * SEEQ_INSERT_WG - 1) / ((uint64_t)SEEQ_INSERT_RUN * SEEQ_INSERT_WG);
+   const uint64_t blocks = (total + (uint64_t)SEEQ_INSERT_RUN * SEEQ_TILE_WG - 1) / ((uint64_t)SEEQ_INSERT_RUN * SEEQ_TILE_WG);
    if (blocks > 0x7FFFFFFFull) { errno = E2BIG; return -1; }
    if (use_device(s->device)) return -1;
    const hipStream_t st = s->stream;
@@ -236,10 +206,8 @@ extern "C" int seeqdevScanInsertText(seeqdev_scan_t *s, const void *d_text, size
    a.out = (uint8_t *)d_out;
    a.cnt = s->d_inscnt;
    HIP_TRY(hipMemsetAsync(&s->d_inscnt->bad, 0, sizeof(uint32_t), st), EIO);
-   hipLaunchKernelGGL(k_insert_text, dim3((unsigned)blocks), dim3(SEEQ_INSERT_WG), 0, st, a);
-   HIP_TRY(hipGetLastError(), EIO);
-   HIP_TRY(hipMemcpyAsync(s->h_inscnt, s->d_inscnt, sizeof(InsertCnt), hipMemcpyDeviceToHost, st), EIO);
-   HIP_TRY(hipStreamSynchronize(st), EIO);
+   hipLaunchKernelGGL(k_insert_text, dim3((unsigned)blocks), dim3(SEEQ_TILE_WG), 0, st, a);
+   if (counters_fetch(s, s->h_inscnt, s->d_inscnt, sizeof(InsertCnt))) return -1;
    if (s->h_inscnt->bad) {
       snprintf(g_last_error, sizeof g_last_error, "insert text: a record lies outside the %zu bytes of text it was given", nbytes);
       errno = EIO;
@@ -251,7 +219,7 @@ extern "C" int seeqdevScanInsertText(seeqdev_scan_t *s, const void *d_text, size
 extern "C" int seeqdevScanLastInsertsMs(const seeqdev_scan_t *s, float *join_ms)
 {
    if (!s || !join_ms) { errno = EINVAL; return -1; }
-   *join_ms = s->ins_join_ms;
+   *join_ms = s->tm_ins.ms;
    return 0;
 }
 

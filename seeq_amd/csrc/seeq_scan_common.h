@@ -194,6 +194,44 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *total,
    return base + x - v;
 }
 
+/* ---- the same for 64-bit values ---- */
+__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d)
+{
+   const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, 64);
+   return ((uint64_t)hi << 32) | lo;
+}
+
+/* inclusive scan over the wave's 64 lanes */
+__device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v)
+{
+   const int lane = threadIdx.x & 63;
+   uint64_t x = v;
+#pragma unroll
+   for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t y = shfl_up_u64(x, d);
+      if (lane >= d) x += y;
+   }
+   return x;
+}
+
+__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t *total, uint64_t *s_wave /* >= 4 */)
+{
+   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+   const uint64_t x = wave_incl_scan_u64(v);
+   if (lane == 63) s_wave[wave] = x;
+   __syncthreads();
+   uint64_t base = 0, tot = 0;
+#pragma unroll
+   for (int w = 0; w < SEEQ_WG / 64; w++) {
+      const uint64_t s = s_wave[w];
+      if (w < wave) base += s;
+      tot += s;
+   }
+   __syncthreads();
+   *total = tot;
+   return base + x - v;
+}
+
 /* Exact per-byte "== '\n'" flags of 4 packed bytes (bit 7 of each byte). */
 __device__ __forceinline__ uint32_t nl_flags(uint32_t w)
 {

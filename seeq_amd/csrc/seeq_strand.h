@@ -19,15 +19,15 @@
  * keys <= its own -- found by a binary search: every output slot is written exactly once, by the one thread that owns the
  * input record.  No atomics on the output, no workgroup waits on another.
  *
- *   k_strand_merge    one thread per input record of either list, tiles of SEEQ_STRAND_TILE (a thread owns records
- *                     tile + k * 256 + tid, as the filter of seeq_fastq.h): the search, then one 16-byte store of the record
- *                     with its strand bit and one 8-byte store of its line offset.  SQ_BEST / SQ_FIRST: the search ends next
- *                     to the other list's record of the same line, if there is one; the loser of the two goes out with
- *                     line number 0 (free: lines are 1-based).
- *   k_strand_reduce   per tile of the MERGED array: records kept (line != 0), kept records that open a line (nmatchlines),
- *                     kept records of the minus strand.
+ *   k_strand_merge    one thread per input record of either list, in the tiles of seeq_tiles.h: the search, then one 16-byte
+ *                     store of the record with its strand bit and one 8-byte store of its line offset.  SQ_BEST / SQ_FIRST:
+ *                     the search ends next to the other list's record of the same line, if there is one; the loser of the two
+ *                     goes out with line number 0 (free: lines are 1-based).
+ *   and over the MERGED array the reduce / top / apply of seeq_tiles.h:
+ *   k_strand_reduce   per tile: records kept (line != 0), kept records that open a line (nmatchlines), kept records of the
+ *                     minus strand.
  *   k_strand_top      one workgroup: exclusive scan of the tiles' kept counts in place; the three totals.
- *   k_strand_apply    (SQ_BEST / SQ_FIRST) the ordered compaction that drops the losers: as k_fastq_apply, no renumbering.
+ *   k_strand_apply    (SQ_BEST / SQ_FIRST) the ordered compaction that drops the losers.
  *
  * The grid comes from the host-known record counts (none: nothing is launched).
  */
@@ -36,9 +36,11 @@
 
 #include <stdint.h>
 
-#define SEEQ_STRAND_WG    256                               /* threads of a workgroup (4 waves) */
-#define SEEQ_STRAND_ITEMS 4                                 /* records per thread */
-#define SEEQ_STRAND_TILE  1024                              /* records per workgroup = SEEQ_STRAND_WG * SEEQ_STRAND_ITEMS */
+#include "seeq_tiles.h"
+
+#define SEEQ_STRAND_WG    SEEQ_TILE_WG                      /* (the host driver prints the shape under the merge's names) */
+#define SEEQ_STRAND_ITEMS SEEQ_TILE_ITEMS
+#define SEEQ_STRAND_TILE  SEEQ_TILE
 #define SEEQ_STRAND_MINUS 0x80000000u                       /* = SEEQDEV_HIT_MINUS (seeq_amd.h) */
 
 #define SEEQ_STRAND_FIRST 0                                 /* = SQ_FIRST, SQ_BEST, SQ_ALL (libseeq.h) */
@@ -126,8 +128,6 @@ SEEQ_ST_HD uint32_t strand_place_minus(int mode, const strand_rec_t *minus, uint
 
 #if defined(__HIPCC__)
 
-static_assert(SEEQ_STRAND_TILE == SEEQ_STRAND_WG * SEEQ_STRAND_ITEMS && SEEQ_STRAND_WG == SEEQ_WG, "merge tile / workgroup");
-
 struct StrandCnt {
    uint32_t kept;                     /* merged records with a line number: the result's records */
    uint32_t opened;                   /* of them, records that open a line: lines with a hit on either strand */
@@ -153,12 +153,11 @@ struct StrandArgs {
    int             mode;              /* SEEQ_STRAND_FIRST / BEST / ALL */
 };
 
-__global__ __launch_bounds__(SEEQ_STRAND_WG) void k_strand_merge(StrandArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_strand_merge(StrandArgs a)
 {
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_STRAND_TILE;
 #pragma unroll
-   for (int k = 0; k < SEEQ_STRAND_ITEMS; k++) {
-      const uint64_t t = base + (uint64_t)k * SEEQ_STRAND_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t t = tile_index(k);
       if (t >= a.n) continue;
       uint4 r;
       uint64_t off;
@@ -184,101 +183,65 @@ __global__ __launch_bounds__(SEEQ_STRAND_WG) void k_strand_merge(StrandArgs a)
    }
 }
 
-__global__ __launch_bounds__(SEEQ_STRAND_WG) void k_strand_reduce(StrandArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_strand_reduce(StrandArgs a)
 {
-   __shared__ uint32_t s_kept[SEEQ_STRAND_WG / 64], s_open[SEEQ_STRAND_WG / 64], s_minus[SEEQ_STRAND_WG / 64];
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_STRAND_TILE;
-   uint32_t kept = 0, opened = 0, minus = 0;                /* wave-uniform */
+   __shared__ uint32_t s_sum[3][SEEQ_TILE_WAVES];
+   uint32_t sum[3] = {0u, 0u, 0u};                          /* kept, opened, minus: wave-uniform */
 #pragma unroll
-   for (int k = 0; k < SEEQ_STRAND_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_STRAND_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = tile_index(k);
       uint4 r = make_uint4(0u, 0u, 0u, 0u);
       if (i < a.n) r = a.mrg[i];
       const bool keep = r.x != 0u;
       /* a loser's line number is 0 and a line's other record, if any, is its neighbour: a kept record opens its line iff the record before it has another number */
-      uint32_t prev = (uint32_t)__shfl_up((int)r.x, 1, 64);         /* lane - 1 holds record i - 1 */
-      if (lane == 0 && i > 0 && i < a.n) prev = a.mrg[i - 1].x;
-      kept += (uint32_t)__popcll(__ballot(keep));
-      opened += (uint32_t)__popcll(__ballot(keep && (i == 0 || prev != r.x)));
-      minus += (uint32_t)__popcll(__ballot(keep && (r.w & SEEQ_STRAND_MINUS) != 0u));
+      const bool opens = tile_opens_line(i, r.x, a.mrg, a.n);
+      sum[0] += (uint32_t)__popcll(__ballot(keep));
+      sum[1] += (uint32_t)__popcll(__ballot(keep && opens));
+      sum[2] += (uint32_t)__popcll(__ballot(keep && (r.w & SEEQ_STRAND_MINUS) != 0u));
    }
-   if (lane == 0) { s_kept[wave] = kept; s_open[wave] = opened; s_minus[wave] = minus; }
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      kept = opened = minus = 0;
-      for (int w = 0; w < SEEQ_STRAND_WG / 64; w++) { kept += s_kept[w]; opened += s_open[w]; minus += s_minus[w]; }
-      a.bsum[blockIdx.x] = kept;
-      a.bsum[a.nt + blockIdx.x] = opened;
-      a.bsum[2 * a.nt + blockIdx.x] = minus;
-   }
+   tile_sums(sum, s_sum, a.bsum, a.nt);
 }
 
 /* One workgroup: bsum[0 .. nt) -> its exclusive prefix, in place; the totals (all below 2^32: at most n). */
-__global__ __launch_bounds__(SEEQ_STRAND_WG) void k_strand_top(StrandArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_strand_top(StrandArgs a)
 {
-   __shared__ uint32_t s_wave[SEEQ_STRAND_WG / 64];
-   uint32_t running = 0, opened = 0, minus = 0;
-   for (uint32_t b0 = 0; b0 < a.nt; b0 += SEEQ_STRAND_WG) {
-      const uint32_t i = b0 + threadIdx.x;
-      const uint32_t v = i < a.nt ? a.bsum[i] : 0u;
-      uint32_t tot;
-      const uint32_t ex = block_excl_scan(v, &tot, s_wave);
-      if (i < a.nt) {
-         a.bsum[i] = running + ex;
-         opened += a.bsum[a.nt + i];
-         minus += a.bsum[2 * a.nt + i];
-      }
-      running += tot;
-   }
-   uint32_t tot_open, tot_minus;
-   block_excl_scan(opened, &tot_open, s_wave);
-   block_excl_scan(minus, &tot_minus, s_wave);
-   if (threadIdx.x == 0) { a.cnt->kept = running; a.cnt->opened = tot_open; a.cnt->minus = tot_minus; }
+   __shared__ uint32_t s_wave[SEEQ_TILE_WAVES];
+   uint32_t tot[3];
+   tile_top(a.bsum, a.nt, s_wave, tot);
+   if (threadIdx.x == 0) { a.cnt->kept = tot[0]; a.cnt->opened = tot[1]; a.cnt->minus = tot[2]; }
 }
 
-__global__ __launch_bounds__(SEEQ_STRAND_WG) void k_strand_apply(StrandArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_strand_apply(StrandArgs a)
 {
-   __shared__ uint32_t s_cnt[SEEQ_STRAND_ITEMS][SEEQ_STRAND_WG / 64];
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_STRAND_TILE;
-   uint4 r[SEEQ_STRAND_ITEMS];
-   uint64_t off[SEEQ_STRAND_ITEMS];
-   uint32_t within[SEEQ_STRAND_ITEMS];                      /* kept records of the wave's round before this lane */
+   __shared__ uint32_t s_cnt[SEEQ_TILE_ITEMS][SEEQ_TILE_WAVES];
+   uint4 r[SEEQ_TILE_ITEMS];
+   uint64_t off[SEEQ_TILE_ITEMS];
+   bool keep[SEEQ_TILE_ITEMS];
+   uint32_t within[SEEQ_TILE_ITEMS];                        /* kept records of the wave's round before this lane */
 #pragma unroll
-   for (int k = 0; k < SEEQ_STRAND_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_STRAND_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = tile_index(k);
       r[k] = make_uint4(0u, 0u, 0u, 0u);
       off[k] = 0;
       if (i < a.n) {
          r[k] = a.mrg[i];
          if (r[k].x != 0u) off[k] = a.mrg_off[i];
       }
-      const uint64_t b = __ballot(r[k].x != 0u);
-      within[k] = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-      if (lane == 0) s_cnt[k][wave] = (uint32_t)__popcll(b);
+      keep[k] = r[k].x != 0u;
+      within[k] = tile_wave_rank(keep[k], s_cnt[k]);
    }
    __syncthreads();
    uint32_t rank0 = a.bsum[blockIdx.x];                     /* kept records before this tile, then before this round */
 #pragma unroll
-   for (int k = 0; k < SEEQ_STRAND_ITEMS; k++) {
-      uint32_t before = 0, tot = 0;
-#pragma unroll
-      for (int w = 0; w < SEEQ_STRAND_WG / 64; w++) {
-         const uint32_t c = s_cnt[k][w];
-         if (w < wave) before += c;
-         tot += c;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint32_t j = tile_place(rank0, within[k], s_cnt[k]);
+      if (!keep[k]) continue;
+      if (j < a.cap_out) {
+         a.out[j] = r[k];
+         a.off_out[j] = off[k];
+      } else {
+         atomicOr(&a.cnt->bad, 1u);
       }
-      if (r[k].x != 0u) {
-         const uint32_t j = rank0 + before + within[k];
-         if (j < a.cap_out) {
-            a.out[j] = r[k];
-            a.off_out[j] = off[k];
-         } else {
-            atomicOr(&a.cnt->bad, 1u);
-         }
-      }
-      rank0 += tot;
    }
 }
 

@@ -38,19 +38,7 @@ static const seeqdev_pattern *pattern_twin(const seeqdev_pattern *pat)
 }
 
 /* the reduction's per-tile sums for n merged records (seeq_strand.h: kept, opened, minus per tile) */
-static size_t strand_bsum_words(size_t n) { return 3 * (n / SEEQ_STRAND_TILE + 2); }
-
-/* The first n records of the scan just fetched, with their offsets, copied aside on the device (16 + 8 bytes per record) before the call's
-   next scan overwrites them: the one owner of the side copy (the both-strands call's plus records, the inserts call's right records).  Waits. */
-static int side_keep(seeqdev_scan *s, size_t n)
-{
-   if (!n) return 0;
-   if (ws_grow(&s->ws, &s->cap_side, n, {{s->side_rec, n * sizeof(seeqdev_hit_t)}, {s->side_off, n * sizeof(uint64_t)}})) return -1;
-   HIP_TRY(hipMemcpyAsync(s->side_rec, s->records, n * sizeof(seeqdev_hit_t), hipMemcpyDeviceToDevice, s->stream), EIO);
-   HIP_TRY(hipMemcpyAsync(s->side_off, s->rec_off, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s->stream), EIO);
-   HIP_TRY(hipStreamSynchronize(s->stream), EIO);            /* the next scan may reallocate the records the copies read */
-   return 0;
-}
+static size_t strand_bsum_words(size_t n) { return 3 * (n / SEEQ_TILE + 2); }
 
 /* Room for n merged records.  Nothing on the stream reads the old blocks: every strands call ends synchronised. */
 static int strands_ws_merged(seeqdev_scan *s, size_t n)
@@ -99,17 +87,15 @@ static int strands_tally(seeqdev_scan *s, StrandArgs &a, const void *rec, uint32
    const hipStream_t st = s->stream;
    a.mrg = (uint4 *)rec;
    a.n = n;
-   a.nt = (uint32_t)(((uint64_t)n + SEEQ_STRAND_TILE - 1) / SEEQ_STRAND_TILE);
+   a.nt = (uint32_t)seeq_tiles_of(n);
    if (strand_bsum_words(s->cap_st_mrg) < 3 * (size_t)a.nt) {
       snprintf(g_last_error, sizeof g_last_error, "both strands: %u records, tile sums for %zu", n, s->cap_st_mrg);
       errno = EIO;
       return -1;
    }
-   hipLaunchKernelGGL(k_strand_reduce, dim3(a.nt), dim3(SEEQ_STRAND_WG), 0, st, a);
-   hipLaunchKernelGGL(k_strand_top, dim3(1), dim3(SEEQ_STRAND_WG), 0, st, a);
-   HIP_TRY(hipGetLastError(), EIO);
-   HIP_TRY(hipMemcpyAsync(s->h_stcnt, s->d_stcnt, sizeof(StrandCnt), hipMemcpyDeviceToHost, st), EIO);
-   HIP_TRY(hipStreamSynchronize(st), EIO);
+   hipLaunchKernelGGL(k_strand_reduce, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_strand_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+   if (counters_fetch(s, s->h_stcnt, s->d_stcnt, sizeof(StrandCnt))) return -1;
    const StrandCnt &h = *s->h_stcnt;
    if (h.bad || h.kept > n || h.opened > h.kept || h.minus > h.kept) {
       snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the strand merge (flags %u, %u of %u kept, %u lines, %u minus)", h.bad, h.kept, n,
@@ -134,7 +120,7 @@ static int strands_merge(seeqdev_scan *s, const StrandSrc &src, int mode, bool f
    }
    const uint32_t n = (uint32_t)n64;
    uint32_t kept = 0, opened = 0, minus = 0;
-   s->st_merge_ms = 0.f;
+   s->tm_st.ms = 0.f;
    if (n) {
       if (strands_ws_merged(s, n)) return -1;
       StrandArgs a;
@@ -142,19 +128,14 @@ static int strands_merge(seeqdev_scan *s, const StrandSrc &src, int mode, bool f
       a.a = (const uint4 *)src.a; a.a_off = src.a_off; a.na = (uint32_t)src.na;
       a.b = (const uint4 *)src.b; a.b_off = src.b_off; a.nb = (uint32_t)src.nb;
       a.mrg = s->st_mrg; a.mrg_off = s->st_mrg_off;
-      a.n = n; a.cap_mrg = (uint32_t)(s->cap_st_mrg < 0xFFFFFFFFull ? s->cap_st_mrg : 0xFFFFFFFFull);
-      a.nt = (uint32_t)(((uint64_t)n + SEEQ_STRAND_TILE - 1) / SEEQ_STRAND_TILE);
+      a.n = n; a.cap_mrg = cap_u32(s->cap_st_mrg);
+      a.nt = (uint32_t)seeq_tiles_of(n);
       a.bsum = s->st_bsum;
       a.cnt = s->d_stcnt;
       a.mode = mode;
-      if (s->prof && !s->have_st_ev) {
-         HIP_TRY(hipEventCreate(&s->ev_st[0]), EIO);
-         HIP_TRY(hipEventCreate(&s->ev_st[1]), EIO);
-         s->have_st_ev = true;
-      }
-      if (s->prof) HIP_TRY(hipEventRecord(s->ev_st[0], st), EIO);
+      if (s->tm_st.begin(s->prof, st)) return -1;
       HIP_TRY(hipMemsetAsync(s->d_stcnt, 0, sizeof(StrandCnt), st), EIO);
-      hipLaunchKernelGGL(k_strand_merge, dim3(a.nt), dim3(SEEQ_STRAND_WG), 0, st, a);
+      hipLaunchKernelGGL(k_strand_merge, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
       if (strands_tally(s, a, s->st_mrg, n)) return -1;      /* (waits: the inputs are read, the record workspace may go) */
       kept = s->h_stcnt->kept;
       /* the result goes to the record workspace, which the inputs have left by now */
@@ -164,14 +145,13 @@ static int strands_merge(seeqdev_scan *s, const StrandSrc &src, int mode, bool f
          HIP_TRY(hipMemcpyAsync(s->rec_off, s->st_mrg_off, (size_t)kept * sizeof(uint64_t), hipMemcpyDeviceToDevice, st), EIO);
       } else if (kept) {
          a.out = (uint4 *)s->records; a.off_out = s->rec_off;
-         a.cap_out = (uint32_t)(s->cap_records < 0xFFFFFFFFull ? s->cap_records : 0xFFFFFFFFull);
-         hipLaunchKernelGGL(k_strand_apply, dim3(a.nt), dim3(SEEQ_STRAND_WG), 0, st, a);
-         HIP_TRY(hipGetLastError(), EIO);
-         HIP_TRY(hipMemcpyAsync(s->h_stcnt, s->d_stcnt, sizeof(StrandCnt), hipMemcpyDeviceToHost, st), EIO);
+         a.cap_out = cap_u32(s->cap_records);
+         hipLaunchKernelGGL(k_strand_apply, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+         if (counters_copy(s, s->h_stcnt, s->d_stcnt, sizeof(StrandCnt))) return -1;
       }
-      if (s->prof) HIP_TRY(hipEventRecord(s->ev_st[1], st), EIO);
+      if (s->tm_st.end(s->prof, st)) return -1;
       HIP_TRY(hipStreamSynchronize(st), EIO);
-      if (s->prof) (void)hipEventElapsedTime(&s->st_merge_ms, s->ev_st[0], s->ev_st[1]);
+      s->tm_st.read(s->prof);
       if (s->h_stcnt->bad) {
          snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the strand merge (an index outside the output)");
          errno = EIO;
@@ -179,21 +159,8 @@ static int strands_merge(seeqdev_scan *s, const StrandSrc &src, int mode, bool f
       }
       if (fastq && kept) {
          /* as fastq_finish: the filtered arrays become the context's records; then the tallies of what is left */
-         if (s->cap_fq != s->cap_records) {
-            snprintf(g_last_error, sizeof g_last_error, "FASTQ filter: scratch for %zu records, record workspace for %zu", s->cap_fq, s->cap_records);
-            errno = EIO;
-            return -1;
-         }
-         if (fastq_launch(s, s->records, s->rec_off, kept, false)) return -1;
-         HIP_TRY(hipStreamSynchronize(st), EIO);
-         const FastqCnt &f = *s->h_fqcnt;
-         if (f.bad || f.kept > kept || f.opened > f.kept) {
-            snprintf(g_last_error, sizeof g_last_error, "internal inconsistency in the FASTQ filter (flags %u, %u of %u kept, %u lines)", f.bad, f.kept, kept, f.opened);
-            errno = EIO;
-            return -1;
-         }
-         seeqdev_hit_t *r = s->records; s->records = s->fq_rec; s->fq_rec = r;
-         uint64_t *o = s->rec_off; s->rec_off = s->fq_off; s->fq_off = o;
+         FastqCnt f;
+         if (fastq_filter_swap(s, kept, &f)) return -1;
          kept = f.kept;
          if (kept) {
             HIP_TRY(hipMemsetAsync(s->d_stcnt, 0, sizeof(StrandCnt), st), EIO);
@@ -274,7 +241,7 @@ extern "C" int seeqdevScanRunStrands(seeqdev_scan_t *s, const seeqdev_pattern_t 
 extern "C" int seeqdevScanLastStrandsMs(const seeqdev_scan_t *s, float *merge_ms)
 {
    if (!s || !merge_ms) { errno = EINVAL; return -1; }
-   *merge_ms = s->st_merge_ms;
+   *merge_ms = s->tm_st.ms;
    return 0;
 }
 

@@ -19,7 +19,7 @@
  *               head to the next head, or to n.
  *   passes      an LSD radix sort by 8-bit digits needs ceil((2 * max_len + 1) / 8) of them, max_len the largest tallied length.
  *
- *   k_tally_pack        one thread per span, tiles of SEEQ_TALLY_TILE (a thread owns spans tile + k * 256 + tid): the record and its
+ *   k_tally_pack        one thread per span, in the tiles of seeq_tiles.h (the sort's tile too): the record and its
  *                       offset, at most 32 text bytes in one or two 16-byte loads issued together (a loop of byte loads waits for
  *                       each in turn: 1.55 ms for 9 M spans, the whole tally 2.03 ms against 0.82 with the wide loads), the key
  *                       stored AT THE SPAN'S OWN INDEX (0: not tallied); per tile one 16-byte {long, foreign, largest L, bad}.
@@ -35,7 +35,8 @@
  *                       lane = ascending index, so the sort is stable.  Every pass is done properly: its histogram is taken from the
  *                       array it permutes (an earlier pass moves keys between tiles, so only pass 0's per-tile populations could be
  *                       had from the unsorted keys).
- *   k_tally_rle_reduce  per tile of the sorted keys: heads, nonzero keys.
+ *   and over the sorted keys the reduce / top / apply of seeq_tiles.h:
+ *   k_tally_rle_reduce  per tile: heads, nonzero keys.
  *   k_tally_rle_top     one workgroup: exclusive scan of the tiles' heads in place; ndistinct, the nonzero keys, the tiles' flags.
  *   k_tally_rle_apply   the ordered compaction of the heads: head j's index in the sorted array -> pos[j] (in the key array the last
  *                       pass left free).
@@ -51,11 +52,12 @@
 
 #include "seeq_strand.h"                                    /* SEEQ_ST_HD, strand_rec_t */
 
-#define SEEQ_TALLY_WG      256                              /* threads of a workgroup (4 waves) */
-#define SEEQ_TALLY_ITEMS   4                                /* keys per thread */
-#define SEEQ_TALLY_TILE    1024                             /* keys per workgroup = SEEQ_TALLY_WG * SEEQ_TALLY_ITEMS: the sort's tile */
-#define SEEQ_TALLY_RADIX   256                              /* values of an 8-bit digit = SEEQ_TALLY_WG: a thread per digit value */
-#define SEEQ_TALLY_CHUNK   1024                             /* matrix entries per workgroup of the offsets scan */
+#define SEEQ_TALLY_WG      SEEQ_TILE_WG                     /* (the host driver prints the shape under the tally's names) */
+#define SEEQ_TALLY_ITEMS   SEEQ_TILE_ITEMS
+#define SEEQ_TALLY_TILE    1024                             /* the sort's tile = SEEQ_TILE, as a number: the tests read it from this file */
+static_assert(SEEQ_TALLY_TILE == SEEQ_TILE, "the tally's tile is seeq_tiles.h's");
+#define SEEQ_TALLY_RADIX   256                             /* values of an 8-bit digit = SEEQ_TILE_WG: a thread per digit value */
+#define SEEQ_TALLY_CHUNK   1024                             /* matrix entries per workgroup of the offsets scan = SEEQ_TILE */
 #define SEEQ_TALLY_LEN_MAX 31                               /* = SEEQDEV_TALLY_MAX_LEN (seeq_amd.h) */
 
 #define SEEQ_TALLY_OK      0                                /* what a span is */
@@ -155,14 +157,13 @@ SEEQ_ST_HD uint32_t tally_digit(uint64_t key, uint32_t pass) { return (uint32_t)
 SEEQ_ST_HD int tally_is_head(uint64_t key, uint64_t prev, int first) { return key != 0u && (first || key != prev); }
 
 /* tiles of n keys; entries of their digit matrix; chunks of its scan */
-SEEQ_ST_HD uint64_t tally_tiles(uint64_t n) { return (n + SEEQ_TALLY_TILE - 1) / SEEQ_TALLY_TILE; }
+SEEQ_ST_HD uint64_t tally_tiles(uint64_t n) { return (n + SEEQ_TILE - 1) / SEEQ_TILE; }
 SEEQ_ST_HD uint64_t tally_matrix(uint64_t n) { return tally_tiles(n) * SEEQ_TALLY_RADIX; }
 SEEQ_ST_HD uint64_t tally_chunks(uint64_t n) { return (tally_matrix(n) + SEEQ_TALLY_CHUNK - 1) / SEEQ_TALLY_CHUNK; }
 
 #if defined(__HIPCC__)
 
-static_assert(SEEQ_TALLY_TILE == SEEQ_TALLY_WG * SEEQ_TALLY_ITEMS && SEEQ_TALLY_WG == SEEQ_WG && SEEQ_TALLY_RADIX == SEEQ_TALLY_WG &&
-              SEEQ_TALLY_CHUNK == SEEQ_TALLY_WG * SEEQ_TALLY_ITEMS, "tally tile / workgroup / radix / chunk");
+static_assert(SEEQ_TALLY_RADIX == SEEQ_TILE_WG && SEEQ_TALLY_CHUNK == SEEQ_TILE, "tally radix / chunk");
 
 struct TallyCnt {
    uint32_t nlong, nforeign;          /* spans not tallied, by kind */
@@ -205,16 +206,16 @@ __device__ __forceinline__ uint32_t tally_wave_max(uint32_t v)
    return v;
 }
 
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_pack(TallyArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_pack(TallyArgs a)
 {
-   __shared__ uint32_t s_long[SEEQ_TALLY_WG / 64], s_for[SEEQ_TALLY_WG / 64], s_max[SEEQ_TALLY_WG / 64], s_bad[SEEQ_TALLY_WG / 64];
+   __shared__ uint32_t s_long[SEEQ_TILE_WG / 64], s_for[SEEQ_TILE_WG / 64], s_max[SEEQ_TILE_WG / 64], s_bad[SEEQ_TILE_WG / 64];
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TALLY_TILE;
+   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TILE;
    uint32_t nlong = 0, nfor = 0;                            /* wave-uniform */
    uint32_t maxl = 0, bad = 0;                              /* this lane's */
 #pragma unroll
-   for (int k = 0; k < SEEQ_TALLY_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_TALLY_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = base + (uint64_t)k * SEEQ_TILE_WG + threadIdx.x;
       int kind = -1;
       if (i < a.n) {
          const uint4 r = a.rec[i];
@@ -254,18 +255,18 @@ __global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_pack(TallyArgs a)
    __syncthreads();
    if (threadIdx.x == 0) {
       uint4 t = make_uint4(0u, 0u, 0u, 0u);
-      for (int w = 0; w < SEEQ_TALLY_WG / 64; w++) { t.x += s_long[w]; t.y += s_for[w]; t.z = s_max[w] > t.z ? s_max[w] : t.z; t.w |= s_bad[w]; }
+      for (int w = 0; w < SEEQ_TILE_WG / 64; w++) { t.x += s_long[w]; t.y += s_for[w]; t.z = s_max[w] > t.z ? s_max[w] : t.z; t.w |= s_bad[w]; }
       a.tstat[blockIdx.x] = t;
    }
 }
 
 /* One workgroup: the tiles' {long, foreign, largest L, bad} -> the totals. */
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_pack_top(TallyArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_pack_top(TallyArgs a)
 {
-   __shared__ uint32_t s_wave[SEEQ_TALLY_WG / 64], s_max[SEEQ_TALLY_WG / 64], s_bad[SEEQ_TALLY_WG / 64];
+   __shared__ uint32_t s_wave[SEEQ_TILE_WG / 64], s_max[SEEQ_TILE_WG / 64], s_bad[SEEQ_TILE_WG / 64];
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
    uint32_t nlong = 0, nfor = 0, maxl = 0, bad = 0;
-   for (uint32_t b0 = 0; b0 < a.nt; b0 += SEEQ_TALLY_WG) {
+   for (uint32_t b0 = 0; b0 < a.nt; b0 += SEEQ_TILE_WG) {
       const uint32_t i = b0 + threadIdx.x;
       if (i < a.nt) {
          const uint4 t = a.tstat[i];
@@ -280,34 +281,34 @@ __global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_pack_top(TallyArgs a)
    if (lane == 0) { s_max[wave] = maxl; s_bad[wave] = bad; }
    __syncthreads();
    if (threadIdx.x == 0) {
-      for (int w = 0; w < SEEQ_TALLY_WG / 64; w++) { maxl = s_max[w] > maxl ? s_max[w] : maxl; bad |= s_bad[w]; }
+      for (int w = 0; w < SEEQ_TILE_WG / 64; w++) { maxl = s_max[w] > maxl ? s_max[w] : maxl; bad |= s_bad[w]; }
       a.cnt->nlong = tot_long; a.cnt->nforeign = tot_for; a.cnt->max_len = maxl; a.cnt->bad = bad;
    }
 }
 
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_hist(TallyArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_hist(TallyArgs a)
 {
    __shared__ uint32_t s_h[SEEQ_TALLY_RADIX];
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TALLY_TILE;
+   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TILE;
    s_h[threadIdx.x] = 0u;
    __syncthreads();
 #pragma unroll
-   for (int k = 0; k < SEEQ_TALLY_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_TALLY_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = base + (uint64_t)k * SEEQ_TILE_WG + threadIdx.x;
       if (i < a.n) atomicAdd(&s_h[tally_digit(a.src[i], a.pass)], 1u);      /* (LDS) */
    }
    __syncthreads();
    a.mat[(uint64_t)threadIdx.x * a.nt + blockIdx.x] = s_h[threadIdx.x];
 }
 
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_scan_reduce(TallyArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_scan_reduce(TallyArgs a)
 {
-   __shared__ uint32_t s_wave[SEEQ_TALLY_WG / 64];
+   __shared__ uint32_t s_wave[SEEQ_TILE_WG / 64];
    const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TALLY_CHUNK;
    uint32_t v = 0;
 #pragma unroll
-   for (int k = 0; k < SEEQ_TALLY_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_TALLY_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = base + (uint64_t)k * SEEQ_TILE_WG + threadIdx.x;
       if (i < a.nmat) v += a.mat[i];
    }
    uint32_t tot;
@@ -316,28 +317,21 @@ __global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_scan_reduce(TallyArgs a
 }
 
 /* One workgroup: bsum[0 .. nb) -> its exclusive prefix, in place. */
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_scan_top(TallyArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_scan_top(TallyArgs a)
 {
-   __shared__ uint32_t s_wave[SEEQ_TALLY_WG / 64];
-   uint32_t running = 0;
-   for (uint32_t b0 = 0; b0 < a.nb; b0 += SEEQ_TALLY_WG) {
-      const uint32_t i = b0 + threadIdx.x;
-      const uint32_t v = i < a.nb ? a.bsum[i] : 0u;
-      uint32_t tot;
-      const uint32_t ex = block_excl_scan(v, &tot, s_wave);
-      if (i < a.nb) a.bsum[i] = running + ex;
-      running += tot;
-   }
+   __shared__ uint32_t s_wave[SEEQ_TILE_WAVES];
+   uint32_t tot[1];
+   tile_top(a.bsum, a.nb, s_wave, tot);
 }
 
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_scan_apply(TallyArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_scan_apply(TallyArgs a)
 {
-   __shared__ uint32_t s_wave[SEEQ_TALLY_WG / 64];
+   __shared__ uint32_t s_wave[SEEQ_TILE_WG / 64];
    const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TALLY_CHUNK;
    uint32_t running = a.bsum[blockIdx.x];
 #pragma unroll
-   for (int k = 0; k < SEEQ_TALLY_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_TALLY_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = base + (uint64_t)k * SEEQ_TILE_WG + threadIdx.x;
       const uint32_t v = i < a.nmat ? a.mat[i] : 0u;
       uint32_t tot;
       const uint32_t ex = block_excl_scan(v, &tot, s_wave);
@@ -346,22 +340,22 @@ __global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_scan_apply(TallyArgs a)
    }
 }
 
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_scatter(TallyArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_scatter(TallyArgs a)
 {
-   __shared__ uint32_t s_cnt[SEEQ_TALLY_ITEMS * (SEEQ_TALLY_WG / 64)][SEEQ_TALLY_RADIX];      /* [round][wave] per digit: count, then destination */
+   __shared__ uint32_t s_cnt[SEEQ_TILE_ITEMS * (SEEQ_TILE_WG / 64)][SEEQ_TALLY_RADIX];      /* [round][wave] per digit: count, then destination */
    __shared__ uint32_t s_bad;
-   constexpr int ROWS = SEEQ_TALLY_ITEMS * (SEEQ_TALLY_WG / 64);
+   constexpr int ROWS = SEEQ_TILE_ITEMS * (SEEQ_TILE_WG / 64);
    const int wave = threadIdx.x >> 6;
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TALLY_TILE;
+   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TILE;
 #pragma unroll
    for (int r = 0; r < ROWS; r++) s_cnt[r][threadIdx.x] = 0u;
    if (threadIdx.x == 0) s_bad = 0u;
    __syncthreads();
-   uint64_t key[SEEQ_TALLY_ITEMS];
-   uint32_t dg[SEEQ_TALLY_ITEMS], within[SEEQ_TALLY_ITEMS];
+   uint64_t key[SEEQ_TILE_ITEMS];
+   uint32_t dg[SEEQ_TILE_ITEMS], within[SEEQ_TILE_ITEMS];
 #pragma unroll
-   for (int k = 0; k < SEEQ_TALLY_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_TALLY_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = base + (uint64_t)k * SEEQ_TILE_WG + threadIdx.x;
       const bool act = i < a.n;
       key[k] = act ? a.src[i] : 0u;
       dg[k] = tally_digit(key[k], a.pass);
@@ -373,7 +367,7 @@ __global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_scatter(TallyArgs a)
          same &= bit ? bal : ~bal;
       }
       within[k] = __builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0u));
-      if (act && within[k] == 0u) s_cnt[k * (SEEQ_TALLY_WG / 64) + wave][dg[k]] = (uint32_t)__popcll(same);
+      if (act && within[k] == 0u) s_cnt[k * (SEEQ_TILE_WG / 64) + wave][dg[k]] = (uint32_t)__popcll(same);
    }
    __syncthreads();
    {
@@ -387,10 +381,10 @@ __global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_scatter(TallyArgs a)
    }
    __syncthreads();
 #pragma unroll
-   for (int k = 0; k < SEEQ_TALLY_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_TALLY_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = base + (uint64_t)k * SEEQ_TILE_WG + threadIdx.x;
       if (i >= a.n) continue;
-      const uint32_t j = s_cnt[k * (SEEQ_TALLY_WG / 64) + wave][dg[k]] + within[k];
+      const uint32_t j = s_cnt[k * (SEEQ_TILE_WG / 64) + wave][dg[k]] + within[k];
       if (j < a.n) a.dst[j] = key[k];
       else s_bad = 1u;
    }
@@ -398,102 +392,68 @@ __global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_scatter(TallyArgs a)
    if (threadIdx.x == 0 && s_bad) a.tstat[blockIdx.x].w = 2u;
 }
 
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_rle_reduce(TallyArgs a)
+/* the run-length pass: the reduce / top / apply of seeq_tiles.h over the sorted keys */
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_rle_reduce(TallyArgs a)
 {
-   __shared__ uint32_t s_head[SEEQ_TALLY_WG / 64], s_nz[SEEQ_TALLY_WG / 64];
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TALLY_TILE;
-   uint32_t heads = 0, nz = 0;                              /* wave-uniform */
+   __shared__ uint32_t s_sum[2][SEEQ_TILE_WAVES];
+   uint32_t sum[2] = {0u, 0u};                              /* heads, nonzero keys: wave-uniform */
 #pragma unroll
-   for (int k = 0; k < SEEQ_TALLY_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_TALLY_WG + threadIdx.x;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = tile_index(k);
       bool head = false, nonzero = false;
       if (i < a.n) {
          const uint64_t key = a.src[i];
          nonzero = key != 0u;
          head = tally_is_head(key, i ? a.src[i - 1] : 0u, i == 0);
       }
-      heads += (uint32_t)__popcll(__ballot(head));
-      nz += (uint32_t)__popcll(__ballot(nonzero));
+      sum[0] += (uint32_t)__popcll(__ballot(head));
+      sum[1] += (uint32_t)__popcll(__ballot(nonzero));
    }
-   if (lane == 0) { s_head[wave] = heads; s_nz[wave] = nz; }
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      heads = nz = 0;
-      for (int w = 0; w < SEEQ_TALLY_WG / 64; w++) { heads += s_head[w]; nz += s_nz[w]; }
-      a.rsum[blockIdx.x] = heads;
-      a.rsum[a.nt + blockIdx.x] = nz;
-   }
+   tile_sums(sum, s_sum, a.rsum, a.nt);
 }
 
 /* One workgroup: rsum[0 .. nt) -> its exclusive prefix, in place; ndistinct, the nonzero keys, the tiles' flags since the pack. */
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_rle_top(TallyArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_rle_top(TallyArgs a)
 {
-   __shared__ uint32_t s_wave[SEEQ_TALLY_WG / 64], s_bad[SEEQ_TALLY_WG / 64];
+   __shared__ uint32_t s_wave[SEEQ_TILE_WAVES], s_bad[SEEQ_TILE_WAVES];
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   uint32_t running = 0, nz = 0, bad = 0;
-   for (uint32_t b0 = 0; b0 < a.nt; b0 += SEEQ_TALLY_WG) {
-      const uint32_t i = b0 + threadIdx.x;
-      const uint32_t v = i < a.nt ? a.rsum[i] : 0u;
-      uint32_t tot;
-      const uint32_t ex = block_excl_scan(v, &tot, s_wave);
-      if (i < a.nt) {
-         a.rsum[i] = running + ex;
-         nz += a.rsum[a.nt + i];
-         bad |= a.tstat[i].w;
-      }
-      running += tot;
-   }
-   uint32_t tot_nz;
-   block_excl_scan(nz, &tot_nz, s_wave);
+   uint32_t tot[2], bad = 0;
+   tile_top(a.rsum, a.nt, s_wave, tot);
+   for (uint32_t i = threadIdx.x; i < a.nt; i += SEEQ_TILE_WG) bad |= a.tstat[i].w;
    bad = __ballot(bad != 0u) != 0ull ? 2u : 0u;
    if (lane == 0) s_bad[wave] = bad;
    __syncthreads();
    if (threadIdx.x == 0) {
-      for (int w = 0; w < SEEQ_TALLY_WG / 64; w++) bad |= s_bad[w];
-      a.cnt->ndistinct = running; a.cnt->nonzero = tot_nz; a.cnt->bad = bad;
+      for (int w = 0; w < SEEQ_TILE_WAVES; w++) bad |= s_bad[w];
+      a.cnt->ndistinct = tot[0]; a.cnt->nonzero = tot[1]; a.cnt->bad = bad;
    }
 }
 
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_rle_apply(TallyArgs a)
+/* the ordered compaction of the heads: a head's index goes to its rank in pos */
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_rle_apply(TallyArgs a)
 {
-   __shared__ uint32_t s_cnt[SEEQ_TALLY_ITEMS][SEEQ_TALLY_WG / 64];
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   const uint64_t base = (uint64_t)blockIdx.x * SEEQ_TALLY_TILE;
-   bool head[SEEQ_TALLY_ITEMS];
-   uint32_t within[SEEQ_TALLY_ITEMS];                       /* heads of the wave's round before this lane */
+   __shared__ uint32_t s_cnt[SEEQ_TILE_ITEMS][SEEQ_TILE_WAVES];
+   bool head[SEEQ_TILE_ITEMS];
+   uint32_t within[SEEQ_TILE_ITEMS];                        /* heads of the wave's round before this lane */
 #pragma unroll
-   for (int k = 0; k < SEEQ_TALLY_ITEMS; k++) {
-      const uint64_t i = base + (uint64_t)k * SEEQ_TALLY_WG + threadIdx.x;
-      head[k] = false;
-      if (i < a.n) head[k] = tally_is_head(a.src[i], i ? a.src[i - 1] : 0u, i == 0);
-      const uint64_t b = __ballot(head[k]);
-      within[k] = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-      if (lane == 63) s_cnt[k][wave] = (uint32_t)__popcll(b);
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint64_t i = tile_index(k);
+      head[k] = i < a.n && tally_is_head(a.src[i], i ? a.src[i - 1] : 0u, i == 0);
+      within[k] = tile_wave_rank(head[k], s_cnt[k]);
    }
    __syncthreads();
    uint32_t rank0 = a.rsum[blockIdx.x];                     /* heads before this tile, then before this round */
 #pragma unroll
-   for (int k = 0; k < SEEQ_TALLY_ITEMS; k++) {
-      uint32_t before = 0, tot = 0;
-#pragma unroll
-      for (int w = 0; w < SEEQ_TALLY_WG / 64; w++) {
-         const uint32_t c = s_cnt[k][w];
-         if (w < wave) before += c;
-         tot += c;
-      }
-      if (head[k]) {
-         const uint32_t j = rank0 + before + within[k];
-         if (j < a.nd) a.pos[j] = (uint32_t)(base + (uint64_t)k * SEEQ_TALLY_WG + threadIdx.x);      /* (nd is the sum of these very heads: k_tally_rle_top) */
-      }
-      rank0 += tot;
+   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
+      const uint32_t j = tile_place(rank0, within[k], s_cnt[k]);
+      if (head[k] && j < a.nd) a.pos[j] = (uint32_t)tile_index(k);      /* (nd is the sum of these very heads: k_tally_rle_top) */
    }
 }
 
 /* One thread per entry of the table; the first head's index goes to the counters (the host checks it against the tallied spans). */
-__global__ __launch_bounds__(SEEQ_TALLY_WG) void k_tally_table(TallyArgs a)
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_table(TallyArgs a)
 {
-   const uint64_t j = (uint64_t)blockIdx.x * SEEQ_TALLY_WG + threadIdx.x;
+   const uint64_t j = (uint64_t)blockIdx.x * SEEQ_TILE_WG + threadIdx.x;
    if (j >= a.nd || j >= a.cap_tab) return;
    const uint32_t p = a.pos[j];
    const uint32_t next = j + 1 < a.nd ? a.pos[j + 1] : a.n;

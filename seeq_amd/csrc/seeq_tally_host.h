@@ -25,15 +25,6 @@ static int tally_fail(const char *what, const TallyCnt &h, uint32_t n, uint64_t 
    return -1;
 }
 
-static int tally_counters(seeqdev_scan *s, TallyCnt *h)
-{
-   HIP_TRY(hipGetLastError(), EIO);
-   HIP_TRY(hipMemcpyAsync(s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt), hipMemcpyDeviceToHost, s->stream), EIO);
-   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-   *h = *s->h_tlcnt;
-   return 0;
-}
-
 /* The table of the n spans rec / off of text[0 .. nbytes); the context's table (tl_tab, tl_n) is the result.  Waits. */
 static int tally_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uint32_t n, const void *d_text, size_t nbytes, seeqdev_tally_counts_t *counts)
 {
@@ -57,17 +48,12 @@ static int tally_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uin
       errno = EIO;
       return -1;
    }
-   if (s->prof && !s->have_tl_ev) {
-      HIP_TRY(hipEventCreate(&s->ev_tl[0]), EIO);
-      HIP_TRY(hipEventCreate(&s->ev_tl[1]), EIO);
-      s->have_tl_ev = true;
-   }
-   if (s->prof) HIP_TRY(hipEventRecord(s->ev_tl[0], st), EIO);
+   if (s->tm_tl.begin(s->prof, st)) return -1;
    HIP_TRY(hipMemsetAsync(s->d_tlcnt, 0, sizeof(TallyCnt), st), EIO);
-   hipLaunchKernelGGL(k_tally_pack, dim3(a.nt), dim3(SEEQ_TALLY_WG), 0, st, a);
-   hipLaunchKernelGGL(k_tally_pack_top, dim3(1), dim3(SEEQ_TALLY_WG), 0, st, a);
-   TallyCnt h;
-   if (tally_counters(s, &h)) return -1;
+   hipLaunchKernelGGL(k_tally_pack, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_tally_pack_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+   if (counters_fetch(s, s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt))) return -1;
+   TallyCnt h = *s->h_tlcnt;
    if (h.bad) {
       snprintf(g_last_error, sizeof g_last_error, "tally: a span lies outside the %zu bytes of text it was given", nbytes);
       errno = EIO;
@@ -81,16 +67,17 @@ static int tally_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uin
       passes = tally_passes(h.max_len);
       for (uint32_t p = 0; p < passes; p++) {
          a.pass = p;
-         hipLaunchKernelGGL(k_tally_hist, dim3(a.nt), dim3(SEEQ_TALLY_WG), 0, st, a);
-         hipLaunchKernelGGL(k_tally_scan_reduce, dim3(a.nb), dim3(SEEQ_TALLY_WG), 0, st, a);
-         hipLaunchKernelGGL(k_tally_scan_top, dim3(1), dim3(SEEQ_TALLY_WG), 0, st, a);
-         hipLaunchKernelGGL(k_tally_scan_apply, dim3(a.nb), dim3(SEEQ_TALLY_WG), 0, st, a);
-         hipLaunchKernelGGL(k_tally_scatter, dim3(a.nt), dim3(SEEQ_TALLY_WG), 0, st, a);
+         hipLaunchKernelGGL(k_tally_hist, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+         hipLaunchKernelGGL(k_tally_scan_reduce, dim3(a.nb), dim3(SEEQ_TILE_WG), 0, st, a);
+         hipLaunchKernelGGL(k_tally_scan_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+         hipLaunchKernelGGL(k_tally_scan_apply, dim3(a.nb), dim3(SEEQ_TILE_WG), 0, st, a);
+         hipLaunchKernelGGL(k_tally_scatter, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
          uint64_t *t = a.src; a.src = a.dst; a.dst = t;     /* (the pass's output is the next one's input) */
       }
-      hipLaunchKernelGGL(k_tally_rle_reduce, dim3(a.nt), dim3(SEEQ_TALLY_WG), 0, st, a);
-      hipLaunchKernelGGL(k_tally_rle_top, dim3(1), dim3(SEEQ_TALLY_WG), 0, st, a);
-      if (tally_counters(s, &h)) return -1;
+      hipLaunchKernelGGL(k_tally_rle_reduce, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+      hipLaunchKernelGGL(k_tally_rle_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+      if (counters_fetch(s, s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt))) return -1;
+      h = *s->h_tlcnt;
       if (h.bad || h.nonzero != ntallied || h.ndistinct > h.nonzero || h.ndistinct == 0) return tally_fail("sort", h, n, ntallied);
       /* the table: a group of its own, grown now that ndistinct is known */
       const size_t nd = h.ndistinct;
@@ -98,15 +85,14 @@ static int tally_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uin
       a.nd = h.ndistinct;
       a.pos = (uint32_t *)a.dst;                           /* (4 bytes per head in the 8 bytes per span the last pass left free) */
       a.tab = (uint4 *)s->tl_tab;
-      a.cap_tab = (uint32_t)(s->cap_tl_tab < 0xFFFFFFFFull ? s->cap_tl_tab : 0xFFFFFFFFull);
-      hipLaunchKernelGGL(k_tally_rle_apply, dim3(a.nt), dim3(SEEQ_TALLY_WG), 0, st, a);
-      hipLaunchKernelGGL(k_tally_table, dim3((unsigned)((nd + SEEQ_TALLY_WG - 1) / SEEQ_TALLY_WG)), dim3(SEEQ_TALLY_WG), 0, st, a);
-      HIP_TRY(hipGetLastError(), EIO);
-      HIP_TRY(hipMemcpyAsync(s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt), hipMemcpyDeviceToHost, st), EIO);
+      a.cap_tab = cap_u32(s->cap_tl_tab);
+      hipLaunchKernelGGL(k_tally_rle_apply, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+      hipLaunchKernelGGL(k_tally_table, dim3((unsigned)((nd + SEEQ_TILE_WG - 1) / SEEQ_TILE_WG)), dim3(SEEQ_TILE_WG), 0, st, a);
+      if (counters_copy(s, s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt))) return -1;
    }
-   if (s->prof) HIP_TRY(hipEventRecord(s->ev_tl[1], st), EIO);
+   if (s->tm_tl.end(s->prof, st)) return -1;
    HIP_TRY(hipStreamSynchronize(st), EIO);
-   if (s->prof) (void)hipEventElapsedTime(&s->tl_ms, s->ev_tl[0], s->ev_tl[1]);
+   s->tm_tl.read(s->prof);
    if (ntallied) {
       h = *s->h_tlcnt;
       /* the counts of the table telescope to n - the first head's index: the keys that are 0 lie before it */
@@ -132,15 +118,7 @@ extern "C" int seeqdevScanTally(seeqdev_scan_t *s, int source, const void *d_tex
          errno = EINVAL;
          return -1;
       }
-      if (!d_text) {
-         if (!s->ins_staged) {
-            snprintf(g_last_error, sizeof g_last_error, "tally: the context holds no staged text of an inserts call");
-            errno = EINVAL;
-            return -1;
-         }
-         d_text = s->d_text;
-         nbytes = s->ins_staged_nbytes;
-      }
+      if (staged_text(s, "tally", &d_text, &nbytes)) return -1;
       rec = s->ins_rec; off = s->ins_off; n = s->ins_n;
    } else {
       /* what seeqdevScanCopyRecords serves: the records of a fetched scan or of a both-strands call.  A context with nothing to fetch
@@ -158,7 +136,7 @@ extern "C" int seeqdevScanTally(seeqdev_scan_t *s, int source, const void *d_tex
    if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
    if (use_device(s->device)) return -1;
    s->tl_n = 0;                                            /* (the table of the call before is gone, whatever comes of this one) */
-   s->tl_ms = 0.f;
+   s->tm_tl.ms = 0.f;
    return tally_run(s, rec, off, (uint32_t)n, d_text, nbytes, counts);
 }
 
@@ -166,20 +144,13 @@ extern "C" const seeqdev_tally_t *seeqdevScanTallyDevice(const seeqdev_scan_t *s
 
 extern "C" int seeqdevScanCopyTally(seeqdev_scan_t *s, seeqdev_tally_t *host_out, size_t first, size_t n)
 {
-   seeqerr = 0;
-   if (!s || (!host_out && n)) { errno = EINVAL; return -1; }
-   if (first > s->tl_n || n > s->tl_n - first) { errno = EINVAL; return -1; }
-   if (n == 0) return 0;
-   if (use_device(s->device)) return -1;
-   HIP_TRY(hipMemcpyAsync(host_out, s->tl_tab + first, n * sizeof(seeqdev_tally_t), hipMemcpyDeviceToHost, s->stream), EIO);
-   HIP_TRY(hipStreamSynchronize(s->stream), EIO);
-   return 0;
+   return copy_out(s, host_out, s ? s->tl_tab : NULL, sizeof(seeqdev_tally_t), s ? s->tl_n : 0, first, n);
 }
 
 extern "C" int seeqdevScanLastTallyMs(const seeqdev_scan_t *s, float *ms)
 {
    if (!s || !ms) { errno = EINVAL; return -1; }
-   *ms = s->tl_ms;
+   *ms = s->tm_tl.ms;
    return 0;
 }
 

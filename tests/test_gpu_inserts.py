@@ -3,11 +3,14 @@ with a right flank under SQ_ALL and a left flank under SQ_BEST or SQ_FIRST, the 
 out of the text there -- against a pure-Python join of two oracle scans by the rule of seeq_insert.h and a host-built insert text."""
 import ctypes as C
 import errno
+import os
 import random
+import re
 
 import numpy as np
 import pytest
 
+from conftest import ROOT
 from oracle.pyoracle import SQ_ALL, SQ_BEST, SQ_CONVERT, SQ_FIRST, SQ_IGNORE
 from test_gpu_strands import _buf, _line_offsets, _mutate, _step
 
@@ -381,6 +384,40 @@ def test_insert_text(gpu, capi, oracle, texts, joined, pats):
             sc.insert_text()
     for p in barcodes:
         p.close()
+    sc.close()
+
+
+def test_inserts_past_one_round_of_the_top_kernel(gpu, capi, oracle, pats):
+    """More inserts than one round of k_insert_top takes (256 tiles: seeq_tiles.h), so that the 64-bit prefix of the text bytes is carried
+    from round to round: the seeded lines of _lines (left flank, short gap, right flank), repeated; the expectation is Joined over the
+    oracle's two scans of the same buffer.  Records, offsets, counts; the gathered text, whose last insert lies at text_bytes minus its
+    own length only if every carry was right."""
+    import torch
+    from seeq_amd import device as dev
+    with open(os.path.join(ROOT, "seeq_amd", "csrc", "seeq_tiles.h")) as f:
+        shape = dict(re.findall(r"^#define\s+(SEEQ_TILE\w*)\s+(\d+)", f.read(), re.M))
+    need = int(shape["SEEQ_TILE"]) * int(shape["SEEQ_TILE_WG"]) + int(shape["SEEQ_TILE"]) + 3
+    window = (0, 0)
+    base = _lines(PAIRS["short"], n=4000, seed=13, kinds=["LR"], gaps=[0, 1, 5, 12])
+    per = len(Joined(oracle, PAIRS["short"], _buf(base), SQ_BEST).rows(window))
+    buf = _buf(base * (need // per + 1))
+    offsets = _line_offsets(buf)
+    j = Joined(oracle, PAIRS["short"], buf, SQ_BEST)
+    rows = j.rows(window)
+    assert len(rows) >= need                                # left records with an admissible right record
+    host_text = _host_text(buf, rows, offsets)
+    last = rows[-1][2] - rows[-1][1] + 1
+    left, right = pats["short"]
+    t = torch.frombuffer(bytearray(buf), dtype=torch.uint8).cuda()
+    sc = dev.Scanner()
+
+    def check(s, res):
+        _check(s, res, j, window, offsets)
+        assert res["text_bytes"] == len(host_text)
+        text = s.insert_text(t).cpu().numpy().tobytes()
+        assert len(text) == len(host_text) and text[len(text) - last:] == host_text[len(host_text) - last:]
+        assert text == host_text
+    _go(sc, "inserts past one round of the top kernel", lambda s: s.inserts_tensor(left, right, t, SQ_BEST, *window), check)
     sc.close()
 
 

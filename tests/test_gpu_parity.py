@@ -1492,6 +1492,27 @@ def test_scanner_reused_across_patterns(gpu, capi, oracle):
     sc.close()
 
 
+def test_copy_entries_check_their_range_without_wrapping(gpu, capi):
+    """seeqdevScanCopyRecords / seeqdevScanCopyOffsets after a fetched scan with records: first + n beyond the records is EINVAL, also
+    where the sum wraps (first = 2^64 - 1, n = 2 adds up to 1); the valid ranges next to it are served."""
+    import errno
+    from seeq_amd import device as dev
+    buf = open(os.path.join(GOLDEN, "reads_small.txt"), "rb").read()
+    pat = dev.Pattern(PAT20, 3)
+    sc = dev.Scanner()
+    n = sc.scan_host(pat, buf, SQ_BEST, dev.WANT_RECORDS)["nrecords"]
+    assert n >= 2
+    L = capi.lib()
+    for entry, width in ((L.seeqdevScanCopyRecords, 16), (L.seeqdevScanCopyOffsets, 8)):
+        out = (C.c_uint8 * (width * 2))()
+        for first, cnt in ((2 ** 64 - 1, 2), (2 ** 64 - 1, 1), (n, 1), (n - 1, 2), (0, n + 1), (1, 2 ** 64 - 1)):
+            C.set_errno(0)
+            assert entry(sc._h, out, first, cnt) == -1 and C.get_errno() == errno.EINVAL, (first, cnt)
+        assert entry(sc._h, out, n - 2, 2) == 0 and entry(sc._h, out, n, 0) == 0
+    sc.close()
+    pat.close()
+
+
 def test_filter_automaton_patterns(gpu, capi, oracle):
     """Patterns whose complete automaton does not fit LDS run k_stream over a partition FILTER automaton; every hit line
     it flags is verified by the exact pass.  configs[4]'s pattern plus random class/N patterns of 24..62 positions at

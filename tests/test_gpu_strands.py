@@ -1,11 +1,14 @@
 """GPU (-m gpu): both strands in one call (seeqdevScanRunStrands / seeqdevScanHostStrands) -- the text scanned with a pattern and with
 its reverse complement, the two record sets merged on the device -- against a pure-Python merge of two oracle scans (of `expr` and of
 revcomp_pattern(expr)) by the rule of seeq_strand.h: SQ_ALL in (line, end, strand) order, SQ_BEST / SQ_FIRST the winner of every line."""
+import os
 import random
+import re
 
 import numpy as np
 import pytest
 
+from conftest import ROOT
 from oracle.pyoracle import SQ_ALL, SQ_BEST, SQ_CONVERT, SQ_FIRST, SQ_IGNORE
 
 pytestmark = pytest.mark.gpu
@@ -202,6 +205,34 @@ def test_strands_vs_merged_oracle_scans(gpu, capi, texts, expected, pats, name, 
     with pytest.raises(dev.SeeqDeviceError):
         sc.fetch()                                          # nothing left to fetch: the call is complete
     sc.close()
+
+
+@pytest.fixture(scope="module")
+def many(oracle):
+    """More records to merge than one round of k_strand_top takes (256 tiles: seeq_tiles.h): the seeded lines of _lines, short ones,
+    repeated until even SQ_BEST leaves tile * wg + tile + 3 records on the two strands together.  -> (buffer, line offsets, that number)"""
+    with open(os.path.join(ROOT, "seeq_amd", "csrc", "seeq_tiles.h")) as f:
+        shape = dict(re.findall(r"^#define\s+(SEEQ_TILE\w*)\s+(\d+)", f.read(), re.M))
+    tile, wg = int(shape["SEEQ_TILE"]), int(shape["SEEQ_TILE_WG"])
+    need = tile * wg + tile + 3
+    base = _lines(PAT20, 3, n=4000, seed=11, lengths=(40, 50, 60))
+    one = Expected(oracle, PAT20, 3, _buf(base), SQ_BEST)
+    buf = _buf(base * (need // (len(one.plus) + len(one.minus)) + 1))
+    return buf, _line_offsets(buf), need
+
+
+@pytest.mark.parametrize("mode", ["all", "best"])
+def test_strands_past_one_round_of_the_top_kernel(gpu, capi, oracle, many, mode):
+    """The expectation is the oracle's two scans of the same (repeated) buffer, merged by Expected as everywhere in this file."""
+    from seeq_amd import device as dev
+    buf, offsets, need = many
+    exp = Expected(oracle, PAT20, 3, buf, MODES[mode])
+    assert len(exp.plus) + len(exp.minus) >= need           # what is merged: the second round of the top kernel runs
+    pat = dev.Pattern(PAT20, 3)
+    sc = dev.Scanner()
+    _check(sc, sc.strands_host(pat, buf, MODES[mode], dev.WANT_RECORDS), exp, offsets)
+    sc.close()
+    pat.close()
 
 
 @pytest.mark.parametrize("name", ["classy", "barcode"])
