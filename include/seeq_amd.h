@@ -437,6 +437,90 @@ int seeqdevScanLastTallyMs(const seeqdev_scan_t * scan, float * ms);
 int seeqdevTallyKey(const char * seq, size_t len, uint64_t * key);
 int seeqdevTallyDecode(uint64_t key, char out[32]);
 
+/* THE GROUPED TALLY: COUNTS PER (GROUP, MEMBER) PAIR.  A UMI family is a pair -- this guide seen with this UMI -- and a pooled screen is a
+ * count matrix of sample x guide: every line carries TWO keys, a group and a member, and what is asked for is the count of each distinct
+ * pair and, per group, its reads and its distinct members.  Two calls, both ON THE DEVICE (seeq_tally_group.h):
+ *   seeqdevScanTallyHold     keeps the keys of one record array as the context's HELD COLUMN: per record its line number and its key
+ *                            (0: no key).  Sources: SEEQDEV_TALLY_INSERTS and SEEQDEV_TALLY_HITS exactly as in seeqdevScanTally (the same
+ *                            preconditions, the same staged text for a NULL text, the same EINVAL cases; the key is seeqdevScanTally's),
+ *                            and SEEQDEV_TALLY_DEMUX: the records seeqdevScanDemuxDevice serves now -- EINVAL without a completed demux
+ *                            call on the context or after a later plain or packed scan on it; the text is ignored and may be NULL; the
+ *                            key is pattern + 1 (1 .. 255: key_bits <= 8, one pass of the sort); a record with margin == 0 is held
+ *                            without a key and counted in nambiguous.  nspans = nheld + nlong + nforeign + nambiguous.  The column
+ *                            belongs to the context: it survives scans, inserts calls, demux calls and plain tallies, and the next hold
+ *                            replaces it (a failed hold leaves none).  A hold over zero records is a valid, empty column.
+ *   seeqdevScanTallyGrouped  pairs the spans of SEEQDEV_TALLY_INSERTS or SEEQDEV_TALLY_HITS (anything else: EINVAL) -- the MEMBERS -- with
+ *                            the held column by line and counts the distinct pairs.  EINVAL without a completed hold, before any device
+ *                            call.  THE CALLER KEEPS THE LINE NUMBERING OF THE TWO CALLS THE SAME: SEEQDEV_FASTQ in both scans or in
+ *                            neither, over the same buffer.
+ *   group of a line          the key of the FIRST held record with that line number (a lower-bound search: several hits of a line under
+ *                            SQ_ALL, the first one decides); 0 when the line has no held record or that record has no key.
+ *   pair                     a member span with key m on a line of group g != 0 is the pair (g, m).  Every other span is counted in
+ *                            exactly one of nlong, nforeign (decided on the member as in the plain tally, long first) and nungrouped (the
+ *                            member has a key, its line has no group): nspans = npaired + nlong + nforeign + nungrouped.
+ *   THE PAIR TABLE           one seeqdev_tally_pair_t per distinct pair, ordered by group, then by member, both as unsigned 64-bit
+ *                            numbers (each in the plain table's order); the counts sum to npaired.  The sparse matrix in row order.
+ *   THE GROUP TABLE          one seeqdev_tally_group_t per distinct group, ascending: count = its reads (the sum of its pairs' counts),
+ *                            first = the rank of its first pair in the pair table, ndistinct = its distinct members -- its pairs are
+ *                            entries [first, first + ndistinct).  The matrix's row index.
+ *   passes                   the plain tally's sort carrying both words: ceil((2 * max_len + 1) / 8) passes over the member word (max_len:
+ *                            the largest PAIRED member length), then ceil(key_bits / 8) over the group word (key_bits: the bit length of
+ *                            the largest held key, which the hold reports); 0 when nothing paired.
+ * Synchronous.  The grouped call reads the record arrays and the held column and writes arrays of its own (it shares the plain tally's
+ * key scratch, not its table): the plain tally's table, the inserts result, the record arrays, the fetch state and the held column are
+ * afterwards what they were.  Its tables -- seeqdevScanTallyPairsDevice / seeqdevScanCopyTallyPairs, seeqdevScanTallyGroupsDevice /
+ * seeqdevScanCopyTallyGroups -- are valid until the context's next grouped call or seeqdevScanFree.  EIO: a span with end < start or one
+ * that reaches beyond nbytes, in either call (checked before any byte of it is loaded; the context stays usable), or an internal
+ * inconsistency (the message names the numbers).  E2BIG: more than 2^32 - 1 records.
+ * Device memory of its own (allocated by a context's first such call, freed with it): 12 bytes per held record (line, key) plus 32 per
+ * tile of 1 024; per member span 16 bytes (the two group-word arrays) beside the plain tally's 17, plus 44 per tile; 24 bytes per
+ * distinct pair and 24 per distinct group.  (The reference counts nothing: an addition of this boundary.) */
+#define SEEQDEV_TALLY_DEMUX 2   /* seeqdevScanTallyHold only: the records seeqdevScanDemuxDevice serves now */
+typedef struct {
+   uint64_t group;
+   uint64_t member;
+   uint64_t count;
+} seeqdev_tally_pair_t;   /* 24 bytes */
+
+typedef struct {
+   uint64_t group;
+   uint64_t count;       /* the group's reads */
+   uint32_t first;       /* rank of its first pair in the pair table */
+   uint32_t ndistinct;   /* its distinct members */
+} seeqdev_tally_group_t;   /* 24 bytes */
+
+typedef struct {
+   uint64_t nspans;      /* records of the source */
+   uint64_t nheld;       /* of them, held with a key */
+   uint64_t nlong;       /* spans of more than SEEQDEV_TALLY_MAX_LEN bytes */
+   uint64_t nforeign;    /* spans of at most that many with a byte that is no base */
+   uint64_t nambiguous;  /* SEEQDEV_TALLY_DEMUX: records with margin == 0 */
+   uint32_t max_len;     /* the largest held length (0 for demux records) */
+   uint32_t key_bits;    /* the bit length of the largest held key */
+} seeqdev_tally_hold_counts_t;   /* 48 bytes */
+
+typedef struct {
+   uint64_t nspans;      /* records of the member source */
+   uint64_t npaired;     /* spans with a key on a line with a group: the sum of the pair table's counts */
+   uint64_t nlong;
+   uint64_t nforeign;
+   uint64_t nungrouped;  /* spans with a key on a line without a group */
+   uint64_t npairs;      /* entries of the pair table */
+   uint64_t ngroups;     /* entries of the group table */
+   uint32_t max_len;     /* the largest paired member length */
+   uint32_t passes;      /* passes of the sort; 0: nothing paired */
+} seeqdev_tally_grouped_counts_t;   /* 64 bytes */
+
+int seeqdevScanTallyHold   (seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_hold_counts_t * counts);
+int seeqdevScanTallyGrouped(seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_grouped_counts_t * counts);
+const seeqdev_tally_pair_t  * seeqdevScanTallyPairsDevice (const seeqdev_scan_t * scan);
+const seeqdev_tally_group_t * seeqdevScanTallyGroupsDevice(const seeqdev_scan_t * scan);
+int seeqdevScanCopyTallyPairs (seeqdev_scan_t * scan, seeqdev_tally_pair_t  * host_out, size_t first, size_t n);
+int seeqdevScanCopyTallyGroups(seeqdev_scan_t * scan, seeqdev_tally_group_t * host_out, size_t first, size_t n);
+/* Device time (ms) of the last grouped call -- its launches and counter copies, between two HIP events on the context's stream (profiling
+ * on; 0 otherwise, and when there was no span). */
+int seeqdevScanLastTallyGroupedMs(const seeqdev_scan_t * scan, float * ms);
+
 /* PACKED READ BATCHES -- 2 bits per base instead of a byte: a quarter of the HBM (and PCIe) traffic of the ASCII scan for
  * read sets that are kept packed anyway (BAM, .2bit, a sequencer's own format).  Layout, all device pointers:
  *   bases : four bases per byte, the FIRST base of a byte in its bits 7-6; code = (ASCII >> 1) & 3, i.e. A 0, C 1, T/U 2, G 3;

@@ -87,6 +87,26 @@ class seeqdev_tally_counts_t(C.Structure):
 
 
 SEEQDEV_TALLY_INSERTS, SEEQDEV_TALLY_HITS, SEEQDEV_TALLY_MAX_LEN = 0, 1, 31
+SEEQDEV_TALLY_DEMUX = 2             # seeqdevScanTallyHold only
+
+
+class seeqdev_tally_pair_t(C.Structure):
+    _fields_ = [("group", C.c_uint64), ("member", C.c_uint64), ("count", C.c_uint64)]
+
+
+class seeqdev_tally_group_t(C.Structure):
+    _fields_ = [("group", C.c_uint64), ("count", C.c_uint64), ("first", C.c_uint32), ("ndistinct", C.c_uint32)]
+
+
+class seeqdev_tally_hold_counts_t(C.Structure):
+    _fields_ = [("nspans", C.c_uint64), ("nheld", C.c_uint64), ("nlong", C.c_uint64), ("nforeign", C.c_uint64), ("nambiguous", C.c_uint64),
+                ("max_len", C.c_uint32), ("key_bits", C.c_uint32)]
+
+
+class seeqdev_tally_grouped_counts_t(C.Structure):
+    _fields_ = [("nspans", C.c_uint64), ("npaired", C.c_uint64), ("nlong", C.c_uint64), ("nforeign", C.c_uint64), ("nungrouped", C.c_uint64),
+                ("npairs", C.c_uint64), ("ngroups", C.c_uint64), ("max_len", C.c_uint32), ("passes", C.c_uint32)]
+
 
 # Every symbol the three public headers declare (tests check the .so exports all of them).
 EXPORTS = [
@@ -108,6 +128,8 @@ EXPORTS = [
     "seeqdevScanRunInserts", "seeqdevScanHostInserts", "seeqdevScanInsertsDevice", "seeqdevScanCopyInserts", "seeqdevScanCopyInsertOffsets",
     "seeqdevScanInsertText", "seeqdevScanLastInsertsMs",
     "seeqdevScanTally", "seeqdevScanTallyDevice", "seeqdevScanCopyTally", "seeqdevScanLastTallyMs", "seeqdevTallyKey", "seeqdevTallyDecode",
+    "seeqdevScanTallyHold", "seeqdevScanTallyGrouped", "seeqdevScanTallyPairsDevice", "seeqdevScanTallyGroupsDevice", "seeqdevScanCopyTallyPairs",
+    "seeqdevScanCopyTallyGroups", "seeqdevScanLastTallyGroupedMs",
     "seeqdevScanLastRuns", "seeqdevScanFallback", "seeqdevScanLastPlan",
 ]
 
@@ -282,6 +304,18 @@ def lib():
     L.seeqdevTallyKey.restype = C.c_int
     L.seeqdevTallyDecode.argtypes = [C.c_uint64, C.c_char_p]
     L.seeqdevTallyDecode.restype = C.c_int
+    L.seeqdevScanTallyHold.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(seeqdev_tally_hold_counts_t)]
+    L.seeqdevScanTallyHold.restype = C.c_int
+    L.seeqdevScanTallyGrouped.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(seeqdev_tally_grouped_counts_t)]
+    L.seeqdevScanTallyGrouped.restype = C.c_int
+    for name in ("seeqdevScanTallyPairsDevice", "seeqdevScanTallyGroupsDevice"):
+        getattr(L, name).argtypes = [C.c_void_p]
+        getattr(L, name).restype = C.c_void_p
+    for name in ("seeqdevScanCopyTallyPairs", "seeqdevScanCopyTallyGroups"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        getattr(L, name).restype = C.c_int
+    L.seeqdevScanLastTallyGroupedMs.argtypes = [C.c_void_p, P(C.c_float)]
+    L.seeqdevScanLastTallyGroupedMs.restype = C.c_int
     L.seeqdevScanPacked.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(seeqdev_packed_t), C.c_int, C.c_int]
     L.seeqdevScanPacked.restype = C.c_int
     L.seeqdevPackReads.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]

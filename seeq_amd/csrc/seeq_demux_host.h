@@ -184,6 +184,7 @@ extern "C" int seeqdevScanRunDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *c
    const int opts = (options & ~(MASK_MATCH | SEEQDEV_FASTQ)) | SQ_BEST;      /* (the set's scans run unflagged: demux_fastq filters their result) */
    if (fastq) s->fq_ws = true;
    s->dm_nrec = 0;
+   s->dm_done = false;
    s->dm_nlines = 0;
    s->multi_n = 0;                                         /* (no multi results on the host: seeqdevScanMultiRecords refuses) */
    s->multi_nrec = 0;
@@ -193,6 +194,7 @@ extern "C" int seeqdevScanRunDemux(seeqdev_scan_t *s, const seeqdev_pattern_t *c
    scan_forget(s);                                         /* (the patterns are the caller's) */
    if (rc == 0 && fastq) rc = demux_fastq(s);
    if (rc) { s->dm_nrec = 0; return -1; }
+   s->dm_done = true;                                      /* (seeqdevScanTallyHold: the records are a result, none included) */
    const DemuxCnt &h = *s->h_dmcnt;
    sum->nlines = s->dm_nlines;
    sum->nassigned = h.nassigned;

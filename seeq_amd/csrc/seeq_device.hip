@@ -111,6 +111,8 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_strand.h"
 #include "seeq_insert.h"
 #include "seeq_tally.h"
+#include "seeq_tally_group.h"
+static_assert(sizeof(seeqdev_tally_pair_t) == 24 && sizeof(seeqdev_tally_group_t) == 24, "pair and group entries are written as three 64-bit words");
 static_assert(sizeof(seeqdev_demux_t) == 16 && sizeof(seeqdev_hit_t) == sizeof(uint4), "demux records are written as uint4");
 static_assert(sizeof(seeqdev_insert_t) == sizeof(uint4), "insert records are written as uint4");
 static_assert(sizeof(seeqdev_tally_t) == sizeof(uint4) && SEEQ_TALLY_LEN_MAX == SEEQDEV_TALLY_MAX_LEN, "tally entries are written as uint4");
@@ -550,6 +552,20 @@ struct seeqdev_scan {
    TallyCnt *d_tlcnt, *h_tlcnt;                           /* h_ pinned */
    size_t    tl_n;                                        /* entries of the last tally's table */
    EventPair tm_tl;                                       /* profiling: around the tally's launches and counter copies */
+   /* seeqdevScanTallyHold / seeqdevScanTallyGrouped (seeq_tally_group.h).  The held column (th_line, th_key: th_n records) is the context's
+      from a completed hold to the next one; the grouped call's key scratch is the plain tally's (tl_key0 / tl_key1 / tl_mat: the member
+      words and the digit matrix) and two group-word arrays of its own; its two tables are valid until the next grouped call */
+   uint32_t *th_line; uint64_t *th_key; uint32_t *th_stat; size_t cap_th;      /* per held record: line, key; per tile: the hold's eight words */
+   size_t    th_n;                                        /* held records */
+   uint32_t  th_key_bits;                                 /* bits of the largest held key */
+   bool      th_done;                                     /* a hold has completed: th_n records (none included) are a column */
+   bool      dm_done;                                     /* a demux has completed: dm_nrec records (none included) are a result */
+   uint64_t *tg_g0, *tg_g1; uint32_t *tg_sum, *tg_stat; size_t cap_tg;         /* per span: the two group-word arrays; per tile: the head sums, the pack's words */
+   seeqdev_tally_pair_t *tg_pairs; size_t cap_tg_pairs;   /* the pair table: one entry per distinct (group, member) */
+   seeqdev_tally_group_t *tg_groups; size_t cap_tg_groups;      /* the group table: one entry per distinct group */
+   TallyGroupCnt *d_tgcnt, *h_tgcnt;                      /* h_ pinned; the hold's counters too */
+   size_t    tg_np, tg_ng;                                /* entries of the last grouped call's tables */
+   EventPair tm_tg;                                       /* profiling: around the grouped call's launches and counter copies */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -574,6 +590,9 @@ struct seeqdev_scan {
    bool sample_dirty;          /* the sampled prefix holds more than one byte outside the alphabet per 4 KB: FASTA input stays off k_pair */
    unsigned sample_age;        /* runs since the line-length sample was taken (a reused buffer may hold other text by now) */
 };
+
+/* the CPU argument-check tests pass a zeroed stand-in of this many bytes for a context: what a check reads before its first device call lies inside */
+static_assert(sizeof(seeqdev_scan) <= 8192, "seeqdev_scan has outgrown the tests' stand-in context");
 
 /* The workspace's hooks (seeq_workspace.h).  A refused allocation (ENOMEM) leaves the array, and with it the capacity its group was sized
    for, as it was: the context stays usable (tests/test_gpu_parity.py::test_a_refused_reserve_leaves_the_context_usable). */
@@ -669,7 +688,7 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
 {
    if (!s) return;
    (void)use_device(s->device);
-   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl})
+   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl, &s->tm_tg})
       if (t->made) { (void)hipEventDestroy(t->ev[0]); (void)hipEventDestroy(t->ev[1]); }
    (void)hipStreamSynchronize(s->stream);
    ws_free_all(&s->ws);
@@ -1839,6 +1858,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 #include "seeq_strand_host.h"
 #include "seeq_insert_host.h"
 #include "seeq_tally_host.h"
+#include "seeq_tally_group_host.h"
 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {

@@ -105,6 +105,34 @@ static int tally_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uin
    return 0;
 }
 
+/* Which record array a source names: SEEQDEV_TALLY_INSERTS or SEEQDEV_TALLY_HITS, with the preconditions of each (EINVAL; the staged text
+   for a NULL text of the inserts) -- shared by seeqdevScanTally and the grouped tally's two calls (seeq_tally_group_host.h). */
+static int tally_source(seeqdev_scan *s, int source, const void **d_text, size_t *nbytes, const uint4 **rec, const uint64_t **off, uint64_t *n)
+{
+   if (source == SEEQDEV_TALLY_INSERTS) {
+      if (!s->ins_done) {
+         snprintf(g_last_error, sizeof g_last_error, "tally: the context holds no result of an inserts call");
+         errno = EINVAL;
+         return -1;
+      }
+      if (staged_text(s, "tally", d_text, nbytes)) return -1;
+      *rec = s->ins_rec; *off = s->ins_off; *n = s->ins_n;
+   } else {
+      /* what seeqdevScanCopyRecords serves: the records of a fetched scan or of a both-strands call.  A context with nothing to fetch
+         (fresh, or after a multi, demux or inserts call: scan_forget) has none; a packed scan's offsets are no offsets into a text */
+      const bool nothing = !s->ran && !s->pat && !s->counts.nlines && !s->counts.nrecords;
+      const bool packed = s->is_packed || (s->d_unpack && s->text == (const void *)s->d_unpack);
+      if (nothing || packed || !*d_text) {
+         snprintf(g_last_error, sizeof g_last_error, "tally: %s", nothing ? "the context holds no fetched records" : packed ? "the records of a packed scan carry no text offsets"
+                                                                                                                       : "the hits need the text they were found in");
+         errno = EINVAL;
+         return -1;
+      }
+      *rec = (const uint4 *)s->records; *off = s->rec_off; *n = s->counts.nrecords;
+   }
+   return 0;
+}
+
 extern "C" int seeqdevScanTally(seeqdev_scan_t *s, int source, const void *d_text, size_t nbytes, seeqdev_tally_counts_t *counts)
 {
    seeqerr = 0;
@@ -112,27 +140,7 @@ extern "C" int seeqdevScanTally(seeqdev_scan_t *s, int source, const void *d_tex
    const uint4 *rec;
    const uint64_t *off;
    uint64_t n;
-   if (source == SEEQDEV_TALLY_INSERTS) {
-      if (!s->ins_done) {
-         snprintf(g_last_error, sizeof g_last_error, "tally: the context holds no result of an inserts call");
-         errno = EINVAL;
-         return -1;
-      }
-      if (staged_text(s, "tally", &d_text, &nbytes)) return -1;
-      rec = s->ins_rec; off = s->ins_off; n = s->ins_n;
-   } else {
-      /* what seeqdevScanCopyRecords serves: the records of a fetched scan or of a both-strands call.  A context with nothing to fetch
-         (fresh, or after a multi, demux or inserts call: scan_forget) has none; a packed scan's offsets are no offsets into a text */
-      const bool nothing = !s->ran && !s->pat && !s->counts.nlines && !s->counts.nrecords;
-      const bool packed = s->is_packed || (s->d_unpack && s->text == (const void *)s->d_unpack);
-      if (nothing || packed || !d_text) {
-         snprintf(g_last_error, sizeof g_last_error, "tally: %s", nothing ? "the context holds no fetched records" : packed ? "the records of a packed scan carry no text offsets"
-                                                                                                                       : "the hits need the text they were found in");
-         errno = EINVAL;
-         return -1;
-      }
-      rec = (const uint4 *)s->records; off = s->rec_off; n = s->counts.nrecords;
-   }
+   if (tally_source(s, source, &d_text, &nbytes, &rec, &off, &n)) return -1;
    if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
    if (use_device(s->device)) return -1;
    s->tl_n = 0;                                            /* (the table of the call before is gone, whatever comes of this one) */

@@ -457,6 +457,67 @@ class Scanner:
         _check(self._lib.seeqdevScanLastTallyMs(self._h, C.byref(ms)))
         return float(ms.value)
 
+    # ---- the grouped tally: counts per (group, member) pair (include/seeq_amd.h: seeqdevScanTallyHold / seeqdevScanTallyGrouped) ----
+    @staticmethod
+    def _text_args(t):
+        return (C.c_void_p(t.data_ptr()) if t is not None else None, t.numel() if t is not None else 0)
+
+    def tally_hold(self, t=None, source="inserts"):
+        """Keep the keys of a record array as this Scanner's held column, the GROUP of every line for tally_grouped: the inserts of the
+        last inserts call ("inserts"), the matches of the records served now ("hits"; of several on a line the first decides), or the
+        winning pattern + 1 of the last demultiplex ("demux"; t is not needed; an ambiguous line is held without a key).  t: as in
+        tally().  -> dict: nspans, nheld, nlong, nforeign, nambiguous, max_len, key_bits.  The column survives scans, inserts calls,
+        demultiplexes and plain tallies; the next tally_hold replaces it."""
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX}.get(source, source)
+        cnt = _capi.seeqdev_tally_hold_counts_t()
+        _check(self._lib.seeqdevScanTallyHold(self._h, src, *self._text_args(t), C.byref(cnt)))
+        return dict(nspans=int(cnt.nspans), nheld=int(cnt.nheld), nlong=int(cnt.nlong), nforeign=int(cnt.nforeign), nambiguous=int(cnt.nambiguous),
+                    max_len=int(cnt.max_len), key_bits=int(cnt.key_bits))
+
+    def tally_grouped(self, t=None, source="inserts", copy=True):
+        """How often each distinct (group, member) pair occurs: the spans of `source` ("inserts" or "hits", as in tally()) are the
+        members, the held column of tally_hold names the group of their line -- paired, sorted and counted on the device.  The two scans
+        must number lines alike (SEEQDEV_FASTQ in both or in neither, the same buffer).  -> dict: nspans, npaired, nlong, nforeign,
+        nungrouped, npairs, ngroups, max_len, passes; copy adds pairs (TALLY_PAIR_DTYPE, ordered by group, then member: the sparse count
+        matrix in row order) and groups (TALLY_GROUP_DTYPE: per group its reads, the rank of its first pair and its distinct members:
+        tally_members).  copy=False leaves both on the device (tally_pairs_device_ptr / tally_pairs_table, tally_groups_device_ptr /
+        tally_groups_table)."""
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS}.get(source, source)
+        cnt = _capi.seeqdev_tally_grouped_counts_t()
+        _check(self._lib.seeqdevScanTallyGrouped(self._h, src, *self._text_args(t), C.byref(cnt)))
+        res = dict(nspans=int(cnt.nspans), npaired=int(cnt.npaired), nlong=int(cnt.nlong), nforeign=int(cnt.nforeign), nungrouped=int(cnt.nungrouped),
+                   npairs=int(cnt.npairs), ngroups=int(cnt.ngroups), max_len=int(cnt.max_len), passes=int(cnt.passes))
+        if copy:
+            res["pairs"] = self.tally_pairs_table(res["npairs"])
+            res["groups"] = self.tally_groups_table(res["ngroups"])
+        return res
+
+    def tally_pairs_table(self, n, first=0):
+        """Copy entries [first, first + n) of the last grouped tally's pair table to the host -> structured array of TALLY_PAIR_DTYPE."""
+        out = np.zeros(n, dtype=TALLY_PAIR_DTYPE)
+        _check(self._lib.seeqdevScanCopyTallyPairs(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def tally_groups_table(self, n, first=0):
+        """Copy entries [first, first + n) of the last grouped tally's group table to the host -> structured array of TALLY_GROUP_DTYPE."""
+        out = np.zeros(n, dtype=TALLY_GROUP_DTYPE)
+        _check(self._lib.seeqdevScanCopyTallyGroups(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def tally_pairs_device_ptr(self):
+        """Device address of the last grouped tally's pair table (seeqdev_tally_pair_t; valid until this Scanner's next grouped tally)."""
+        return self._lib.seeqdevScanTallyPairsDevice(self._h)
+
+    def tally_groups_device_ptr(self):
+        """Device address of the last grouped tally's group table (seeqdev_tally_group_t; valid until this Scanner's next grouped tally)."""
+        return self._lib.seeqdevScanTallyGroupsDevice(self._h)
+
+    def last_tally_grouped_ms(self):
+        """Device time of the last grouped tally (its launches and counter copies; profiling on), 0 when not measured."""
+        ms = C.c_float(0)
+        _check(self._lib.seeqdevScanLastTallyGroupedMs(self._h, C.byref(ms)))
+        return float(ms.value)
+
     # ---- several patterns, one text (include/seeq_amd.h: seeqdevScanRunMulti / seeqdevScanHostMulti) ----
     def _multi(self, patterns, call, want, copy=True):
         n = len(patterns)
@@ -575,6 +636,23 @@ def tally_lookup(result, sequences):
         hit = keys[at] == want
         out[hit] = counts[at[hit]]
     return out
+
+
+# One entry of seeqdevScanTallyGrouped's pair table / group table (seeq_amd.h: seeqdev_tally_pair_t, seeqdev_tally_group_t, 24 bytes each).
+TALLY_PAIR_DTYPE = np.dtype([("group", "<u8"), ("member", "<u8"), ("count", "<u8")])
+TALLY_GROUP_DTYPE = np.dtype([("group", "<u8"), ("count", "<u8"), ("first", "<u4"), ("ndistinct", "<u4")])
+
+
+def tally_members(result, group):
+    """The pairs of one group from a tally_grouped() result (copy=True): the slice of result["pairs"] that the group's entry of
+    result["groups"] names, found by a binary search over the group keys; empty when the group was not seen.  group: the key (an int:
+    tally_key(sequence), or pattern + 1 after a demux hold)."""
+    groups, pairs = result["groups"], result["pairs"]
+    at = int(np.searchsorted(groups["group"], np.uint64(group)))
+    if at == len(groups) or int(groups["group"][at]) != int(group):
+        return pairs[:0]
+    first = int(groups["first"][at])
+    return pairs[first:first + int(groups["ndistinct"][at])]
 
 
 # One record of seeqdevScanRunDemux (seeq_amd.h: seeqdev_demux_t, 16 bytes).
