@@ -521,6 +521,54 @@ int seeqdevScanCopyTallyGroups(seeqdev_scan_t * scan, seeqdev_tally_group_t * ho
  * on; 0 otherwise, and when there was no span). */
 int seeqdevScanLastTallyGroupedMs(const seeqdev_scan_t * scan, float * ms);
 
+/* COUNTING AGAINST A KNOWN LIBRARY: EXACT OR ONE MISMATCH.  The sequences of a screen or a barcode run are known in advance -- a guide
+ * library, a whitelist -- and what is asked for is one count per library ENTRY, a read with one sequencing error counted for the entry it
+ * came from.  seeqdevScanTally counts distinct OBSERVED sequences: every erroneous copy is a row of its own.  With a library set on the
+ * context, a span's key is replaced ON THE DEVICE (seeq_tally_library.h) by its entry's id before the tally's sort, which then runs
+ * ceil(bitlen(N) / 8) passes over ids instead of ceil((2 * max_len + 1) / 8) over sequences.
+ *   seeqdevScanSetLibrary    keys[0 .. n): values of seeqdevTallyKey, pairwise distinct, lengths mixed freely.  THE ID of keys[i] is i + 1;
+ *                            id 0 is "no entry".  Validated on the host before any device call: EINVAL for a NULL scan, NULL keys with
+ *                            n > 0, max_mismatch outside {0, 1}, a value that is no key or a duplicate (seeqdevLastError names the
+ *                            index); E2BIG for n > 2^24 - 1.  The library belongs to the context: it survives scans, inserts calls, demux
+ *                            calls, plain and grouped tallies and holds; the next set call replaces it, a failed one leaves none, n == 0
+ *                            clears it, seeqdevScanFree frees it.
+ *   neighbour                of a key k of length L: k ^ (s << 2(L - 1 - p)), 0 <= p < L, s in {1, 2, 3} -- another base at position p.
+ *                            Substitutions only: an insertion or deletion changes the length and makes no neighbour.
+ *   assignment               of a span's key k: k is in the library -> its id, EXACT (even when neighbours of k are entries too).  Else,
+ *                            under max_mismatch 1, with H the entries that are neighbours of k: |H| == 1 -> that id, CORRECTED;
+ *                            |H| >= 2 -> 0, AMBIGUOUS; |H| == 0 -> 0, UNKNOWN.  Else, under max_mismatch 0 -> 0, UNKNOWN.  Long and
+ *                            foreign spans are decided first, exactly as in seeqdevScanTally; the library never sees them.
+ *                            nspans = nexact + ncorrected + nambiguous + nunknown + nlong + nforeign; nassigned = nexact + ncorrected.
+ *   seeqdevScanTallyLibrary  sources, preconditions, staged text, EINVAL / EIO / E2BIG cases: seeqdevScanTally's, unchanged; EINVAL
+ *                            without a library, before any device call.  THE TABLE is the context's tally table -- one seeqdev_tally_t
+ *                            {key = id, count} per id that occurs, ids ascending, the counts summing to nassigned, entries without a read
+ *                            absent -- served by seeqdevScanTallyDevice / seeqdevScanCopyTally and replaced by the next tally of either
+ *                            kind; seeqdevScanLastTallyMs reports its time.  passes = ceil(bitlen(N) / 8), 0 when nothing was assigned.
+ *   seeqdevScanTallyHoldLibrary  holds the column as seeqdevScanTallyHold does for SEEQDEV_TALLY_INSERTS / SEEQDEV_TALLY_HITS
+ *                            (SEEQDEV_TALLY_DEMUX: EINVAL), then assigns it: the held key of a record is its entry's id, or 0.
+ *                            key_bits = bitlen(N); ndistinct and passes are 0.  A following seeqdevScanTallyGrouped runs unchanged: its
+ *                            group table has one row per library entry seen, erroneous guides folded into their entry.
+ * Synchronous.  Device memory of its own: 12 bytes per library entry (key, id), 8 bytes per tile of 1 024 spans and 16 per 64 misses;
+ * the miss indices (4 bytes per miss) lie in the tally's second key array, which the sort has not touched yet (the hold call allocates
+ * the plain tally's key scratch for them).  (The reference counts nothing: an addition of this boundary.) */
+typedef struct {
+   uint64_t nspans;      /* records of the source */
+   uint64_t nassigned;   /* nexact + ncorrected: the sum of the table's counts */
+   uint64_t nexact;      /* spans whose key is a library entry */
+   uint64_t ncorrected;  /* spans one substitution away from exactly one entry */
+   uint64_t nambiguous;  /* ... from two or more */
+   uint64_t nunknown;    /* spans with a key that is neither */
+   uint64_t nlong;       /* spans of more than SEEQDEV_TALLY_MAX_LEN bytes */
+   uint64_t nforeign;    /* spans of at most that many with a byte that is no base */
+   uint64_t ndistinct;   /* entries of the table (the hold: 0) */
+   uint32_t key_bits;    /* bitlen(N) */
+   uint32_t passes;      /* passes of the sort: ceil(key_bits / 8); 0: nothing was assigned (the hold: 0) */
+} seeqdev_tally_library_counts_t;   /* 80 bytes */
+
+int seeqdevScanSetLibrary(seeqdev_scan_t * scan, const uint64_t * keys, size_t n, int max_mismatch);
+int seeqdevScanTallyLibrary    (seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_library_counts_t * counts);
+int seeqdevScanTallyHoldLibrary(seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_library_counts_t * counts);
+
 /* PACKED READ BATCHES -- 2 bits per base instead of a byte: a quarter of the HBM (and PCIe) traffic of the ASCII scan for
  * read sets that are kept packed anyway (BAM, .2bit, a sequencer's own format).  Layout, all device pointers:
  *   bases : four bases per byte, the FIRST base of a byte in its bits 7-6; code = (ASCII >> 1) & 3, i.e. A 0, C 1, T/U 2, G 3;

@@ -108,6 +108,12 @@ class seeqdev_tally_grouped_counts_t(C.Structure):
                 ("npairs", C.c_uint64), ("ngroups", C.c_uint64), ("max_len", C.c_uint32), ("passes", C.c_uint32)]
 
 
+class seeqdev_tally_library_counts_t(C.Structure):
+    _fields_ = [("nspans", C.c_uint64), ("nassigned", C.c_uint64), ("nexact", C.c_uint64), ("ncorrected", C.c_uint64), ("nambiguous", C.c_uint64),
+                ("nunknown", C.c_uint64), ("nlong", C.c_uint64), ("nforeign", C.c_uint64), ("ndistinct", C.c_uint64), ("key_bits", C.c_uint32),
+                ("passes", C.c_uint32)]
+
+
 # Every symbol the three public headers declare (tests check the .so exports all of them).
 EXPORTS = [
     # libseeq.h
@@ -130,6 +136,7 @@ EXPORTS = [
     "seeqdevScanTally", "seeqdevScanTallyDevice", "seeqdevScanCopyTally", "seeqdevScanLastTallyMs", "seeqdevTallyKey", "seeqdevTallyDecode",
     "seeqdevScanTallyHold", "seeqdevScanTallyGrouped", "seeqdevScanTallyPairsDevice", "seeqdevScanTallyGroupsDevice", "seeqdevScanCopyTallyPairs",
     "seeqdevScanCopyTallyGroups", "seeqdevScanLastTallyGroupedMs",
+    "seeqdevScanSetLibrary", "seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary",
     "seeqdevScanLastRuns", "seeqdevScanFallback", "seeqdevScanLastPlan",
 ]
 
@@ -316,6 +323,11 @@ def lib():
         getattr(L, name).restype = C.c_int
     L.seeqdevScanLastTallyGroupedMs.argtypes = [C.c_void_p, P(C.c_float)]
     L.seeqdevScanLastTallyGroupedMs.restype = C.c_int
+    L.seeqdevScanSetLibrary.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    L.seeqdevScanSetLibrary.restype = C.c_int
+    for name in ("seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(seeqdev_tally_library_counts_t)]
+        getattr(L, name).restype = C.c_int
     L.seeqdevScanPacked.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(seeqdev_packed_t), C.c_int, C.c_int]
     L.seeqdevScanPacked.restype = C.c_int
     L.seeqdevPackReads.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]

@@ -23,7 +23,7 @@
  * Here: plumbing, pattern handle, scan context, the segment and packed drivers, the scan
  * entries.  The side entries are included where they belong in that order: seeq_synth.h,
  * seeq_text_alloc.h, seeq_multi_host.h, seeq_demux_host.h, seeq_strand_host.h, seeq_insert_host.h,
- * seeq_tally_host.h, seeq_string.h.
+ * seeq_tally_host.h, seeq_tally_group_host.h, seeq_tally_library_host.h, seeq_string.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -112,6 +112,7 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_insert.h"
 #include "seeq_tally.h"
 #include "seeq_tally_group.h"
+#include "seeq_tally_library.h"
 static_assert(sizeof(seeqdev_tally_pair_t) == 24 && sizeof(seeqdev_tally_group_t) == 24, "pair and group entries are written as three 64-bit words");
 static_assert(sizeof(seeqdev_demux_t) == 16 && sizeof(seeqdev_hit_t) == sizeof(uint4), "demux records are written as uint4");
 static_assert(sizeof(seeqdev_insert_t) == sizeof(uint4), "insert records are written as uint4");
@@ -566,6 +567,15 @@ struct seeqdev_scan {
    TallyGroupCnt *d_tgcnt, *h_tgcnt;                      /* h_ pinned; the hold's counters too */
    size_t    tg_np, tg_ng;                                /* entries of the last grouped call's tables */
    EventPair tm_tg;                                       /* profiling: around the grouped call's launches and counter copies */
+   /* seeqdevScanSetLibrary / seeqdevScanTallyLibrary / seeqdevScanTallyHoldLibrary (seeq_tally_library.h).  The library (lb_key, lb_id: lb_n
+      entries, sorted by key) is the context's from a completed set call to the next one; the assignment's scratch is allocated by the first
+      library call */
+   uint64_t *lb_key; uint32_t *lb_id; size_t cap_lb;      /* per entry: key, id */
+   size_t    lb_n;                                        /* entries of the library; 0: the context holds none */
+   int       lb_mismatch;                                 /* its max_mismatch: 0 or 1 */
+   uint32_t *lb_sum; size_t cap_lb_sum;                   /* per tile of spans: misses, exact */
+   uint4    *lb_nstat; size_t cap_lb_near;                /* per workgroup of the near pass: corrected, ambiguous, unknown, bad */
+   TallyLibCnt *d_lbcnt, *h_lbcnt;                        /* h_ pinned */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -1859,6 +1869,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 #include "seeq_insert_host.h"
 #include "seeq_tally_host.h"
 #include "seeq_tally_group_host.h"
+#include "seeq_tally_library_host.h"
 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {

@@ -1,0 +1,264 @@
+/*
+ * seeq_tally_library_host.h -- the host driver of the tally against a known library (rule and kernels: seeq_tally_library.h): the set
+ * call's validation, sort and upload, the assignment of a key array in place -- the exact pass, and under max_mismatch 1 the compaction of
+ * the misses and the near pass -- between the plain tally's pack (or the grouped tally's hold) and what follows it, and the
+ * seeqdevScanSetLibrary / seeqdevScanTallyLibrary / seeqdevScanTallyHoldLibrary entries.  Included by seeq_device.hip behind
+ * seeq_tally_group_host.h.
+ */
+#ifndef SEEQ_TALLY_LIBRARY_HOST_H_
+#define SEEQ_TALLY_LIBRARY_HOST_H_
+
+#include <vector>
+
+static int tally_library_fail(const char *what, const TallyLibCnt &l, const TallyCnt &h, uint32_t n, uint64_t nkeyed, uint64_t nassigned, size_t nlib)
+{
+   snprintf(g_last_error, sizeof g_last_error,
+            "internal inconsistency in the library tally (%s: flags %u / %u, %u spans, %llu with a key, %u exact, %u misses, %u corrected, %u ambiguous, %u unknown, "
+            "%llu assigned, %u nonzero ids, %u distinct of %zu entries, first head %u)",
+            what, l.bad, h.bad, n, (unsigned long long)nkeyed, l.nexact, l.nmiss, l.ncorrected, l.nambiguous, l.nunknown, (unsigned long long)nassigned, h.nonzero,
+            h.ndistinct, nlib, h.first);
+   errno = EIO;
+   return -1;
+}
+
+extern "C" int seeqdevScanSetLibrary(seeqdev_scan_t *s, const uint64_t *keys, size_t n, int max_mismatch)
+{
+   seeqerr = 0;
+   if (!s) { errno = EINVAL; return -1; }
+   s->lb_n = 0;                                            /* (the library of before is gone, whatever comes of this call) */
+   s->lb_mismatch = 0;
+   if ((!keys && n) || (max_mismatch != 0 && max_mismatch != 1)) { errno = EINVAL; return -1; }
+   if (!n) return 0;
+   if (n > SEEQ_TLIB_MAX) {
+      snprintf(g_last_error, sizeof g_last_error, "library: %zu entries, at most %u", n, SEEQ_TLIB_MAX);
+      errno = E2BIG;
+      return -1;
+   }
+   std::vector<uint64_t> skey(n);
+   std::vector<uint32_t> sid(n);
+   size_t at;
+   const int bad = tally_lib_prepare(keys, n, skey.data(), sid.data(), &at);
+   if (bad) {
+      snprintf(g_last_error, sizeof g_last_error, bad == SEEQ_TLIB_E_NOKEY ? "library: entry %zu (%#llx) is no tally key" : "library: entry %zu (%#llx) repeats an earlier entry",
+               at, (unsigned long long)keys[at]);
+      errno = EINVAL;
+      return -1;
+   }
+   if (use_device(s->device)) return -1;
+   if (ws_grow(&s->ws, &s->cap_lb, n, {{s->lb_key, n * sizeof(uint64_t)}, {s->lb_id, n * sizeof(uint32_t)}})) return -1;
+   HIP_TRY(hipMemcpyAsync(s->lb_key, skey.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream), EIO);
+   HIP_TRY(hipMemcpyAsync(s->lb_id, sid.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream), EIO);
+   HIP_TRY(hipStreamSynchronize(s->stream), EIO);            /* (the host copies go with this call) */
+   s->lb_n = n;
+   s->lb_mismatch = max_mismatch;
+   return 0;
+}
+
+/* key[0 .. n), n > 0, the spans' keys -> their ids against the context's library, in place; miss: room for 4 bytes per span that nothing
+   else uses until this returns.  *l: the five counts, checked against nkeyed, the nonzero keys.  Waits. */
+static int tally_library_assign(seeqdev_scan *s, uint64_t *key, uint32_t *miss, uint32_t n, uint64_t nkeyed, TallyLibCnt *l)
+{
+   const hipStream_t st = s->stream;
+   const size_t nt = (size_t)tally_tiles(n);
+   if (ws_make(&s->ws, {{s->d_lbcnt, sizeof(TallyLibCnt)}, {s->h_lbcnt, sizeof(TallyLibCnt), WS_PINNED}})) return -1;
+   if (ws_grow(&s->ws, &s->cap_lb_sum, nt, {{s->lb_sum, 2 * nt * sizeof(uint32_t)}})) return -1;
+   TallyLibArgs a;
+   memset(&a, 0, sizeof a);
+   a.key = key; a.n = n; a.nt = (uint32_t)nt;
+   a.lkey = s->lb_key; a.lid = s->lb_id; a.nlib = (uint32_t)s->lb_n;
+   a.stride = tally_lib_stride(a.nlib); a.probes = tally_lib_probes(a.stride);
+   a.near = s->lb_mismatch ? 1u : 0u;
+   a.esum = s->lb_sum;
+   a.miss = miss;
+   a.cnt = s->d_lbcnt;
+   const TallyCnt none = {};
+   if (!s->lb_n || s->lb_n > s->cap_lb || s->lb_n > SEEQ_TLIB_MAX || nt > s->cap_lb_sum) {
+      snprintf(g_last_error, sizeof g_last_error, "library tally: %zu entries, arrays for %zu; %zu tiles, sums for %zu", s->lb_n, s->cap_lb, nt, s->cap_lb_sum);
+      errno = EIO;
+      return -1;
+   }
+   HIP_TRY(hipMemsetAsync(s->d_lbcnt, 0, sizeof(TallyLibCnt), st), EIO);
+   hipLaunchKernelGGL(k_tally_assign_exact, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_tally_assign_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+   if (counters_fetch(s, s->h_lbcnt, s->d_lbcnt, sizeof(TallyLibCnt))) return -1;
+   *l = *s->h_lbcnt;
+   if ((uint64_t)l->nexact + l->nmiss != nkeyed) return tally_library_fail("exact", *l, none, n, nkeyed, 0, s->lb_n);
+   if (!a.near) { l->nunknown = l->nmiss; return 0; }      /* max_mismatch 0: a miss is unknown, and 0 stands at its index already */
+   if (!l->nmiss) return 0;                                /* no miss: the near pass is not launched */
+   a.nmiss = l->nmiss;
+   a.nwg = (uint32_t)(((uint64_t)a.nmiss + SEEQ_TLIB_NEAR_WG * SEEQ_TLIB_NEAR_ROUNDS - 1) / (SEEQ_TLIB_NEAR_WG * SEEQ_TLIB_NEAR_ROUNDS));
+   if (ws_grow(&s->ws, &s->cap_lb_near, a.nwg, {{s->lb_nstat, (size_t)a.nwg * sizeof(uint4)}})) return -1;
+   a.nstat = s->lb_nstat;
+   if ((size_t)a.nwg > s->cap_lb_near) {
+      snprintf(g_last_error, sizeof g_last_error, "library tally: %u workgroups of the near pass, room for %zu", a.nwg, s->cap_lb_near);
+      errno = EIO;
+      return -1;
+   }
+   hipLaunchKernelGGL(k_tally_miss_apply, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_tally_assign_near, dim3(a.nwg), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_tally_near_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+   if (counters_fetch(s, s->h_lbcnt, s->d_lbcnt, sizeof(TallyLibCnt))) return -1;
+   *l = *s->h_lbcnt;
+   if (l->bad || (uint64_t)l->nexact + l->nmiss != nkeyed || (uint64_t)l->ncorrected + l->nambiguous + l->nunknown != l->nmiss)
+      return tally_library_fail("near", *l, none, n, nkeyed, 0, s->lb_n);
+   return 0;
+}
+
+static void tally_library_counts(seeqdev_tally_library_counts_t *counts, const TallyLibCnt &l)
+{
+   counts->nexact = l.nexact; counts->ncorrected = l.ncorrected; counts->nambiguous = l.nambiguous; counts->nunknown = l.nunknown;
+   counts->nassigned = (uint64_t)l.nexact + l.ncorrected;
+}
+
+/* The table of the n spans rec / off of text[0 .. nbytes) against the library; the context's table (tl_tab, tl_n) is the result: tally_run
+   with the assignment between its pack and its sort, and the sort's passes from the library's size.  Waits. */
+static int tally_library_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uint32_t n, const void *d_text, size_t nbytes,
+                             seeqdev_tally_library_counts_t *counts)
+{
+   const hipStream_t st = s->stream;
+   memset(counts, 0, sizeof *counts);
+   counts->nspans = n;
+   counts->key_bits = tally_lib_bitlen(s->lb_n);
+   if (!n) return 0;                                       /* no spans: nothing is launched */
+   if (tally_ws_keys(s, n)) return -1;
+   TallyArgs a;
+   memset(&a, 0, sizeof a);
+   a.rec = rec; a.off = off; a.n = n;
+   a.nt = (uint32_t)tally_tiles(n);
+   a.text = (const uint8_t *)d_text; a.nbytes = nbytes;
+   a.src = s->tl_key0; a.dst = s->tl_key1;
+   a.mat = s->tl_mat; a.nmat = (uint32_t)tally_matrix(n); a.nb = (uint32_t)tally_chunks(n);
+   a.rsum = s->tl_sum; a.bsum = s->tl_sum + 2 * (size_t)a.nt;
+   a.tstat = s->tl_stat;
+   a.cnt = s->d_tlcnt;
+   if ((size_t)n > s->cap_tl || tally_tiles(s->cap_tl) < a.nt || tally_chunks(s->cap_tl) < a.nb) {
+      snprintf(g_last_error, sizeof g_last_error, "library tally: %u spans, arrays for %zu", n, s->cap_tl);
+      errno = EIO;
+      return -1;
+   }
+   if (s->tm_tl.begin(s->prof, st)) return -1;
+   HIP_TRY(hipMemsetAsync(s->d_tlcnt, 0, sizeof(TallyCnt), st), EIO);
+   hipLaunchKernelGGL(k_tally_pack, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+   hipLaunchKernelGGL(k_tally_pack_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+   if (counters_fetch(s, s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt))) return -1;
+   TallyCnt h = *s->h_tlcnt;
+   if (h.bad) {
+      snprintf(g_last_error, sizeof g_last_error, "library tally: a span lies outside the %zu bytes of text it was given", nbytes);
+      errno = EIO;
+      return -1;
+   }
+   TallyLibCnt l = {};
+   if ((uint64_t)h.nlong + h.nforeign > n || h.max_len > SEEQ_TALLY_LEN_MAX) return tally_library_fail("pack", l, h, n, 0, 0, s->lb_n);
+   const uint64_t nkeyed = (uint64_t)n - h.nlong - h.nforeign;
+   const TallyCnt packed = h;
+   if (nkeyed && tally_library_assign(s, a.src, (uint32_t *)a.dst, n, nkeyed, &l)) return -1;      /* (4 bytes per miss in the 8 per span the sort has not touched yet) */
+   const uint64_t nassigned = (uint64_t)l.nexact + l.ncorrected;
+   if ((uint64_t)l.nexact + l.ncorrected + l.nambiguous + l.nunknown + packed.nlong + packed.nforeign != n)
+      return tally_library_fail("kinds", l, h, n, nkeyed, nassigned, s->lb_n);
+   const uint32_t passes = tally_lib_passes(nassigned, (uint32_t)s->lb_n);
+   if (nassigned) {
+      for (uint32_t p = 0; p < passes; p++) {
+         a.pass = p;
+         hipLaunchKernelGGL(k_tally_hist, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+         hipLaunchKernelGGL(k_tally_scan_reduce, dim3(a.nb), dim3(SEEQ_TILE_WG), 0, st, a);
+         hipLaunchKernelGGL(k_tally_scan_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+         hipLaunchKernelGGL(k_tally_scan_apply, dim3(a.nb), dim3(SEEQ_TILE_WG), 0, st, a);
+         hipLaunchKernelGGL(k_tally_scatter, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+         uint64_t *t = a.src; a.src = a.dst; a.dst = t;     /* (the pass's output is the next one's input) */
+      }
+      hipLaunchKernelGGL(k_tally_rle_reduce, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+      hipLaunchKernelGGL(k_tally_rle_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
+      if (counters_fetch(s, s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt))) return -1;
+      h = *s->h_tlcnt;
+      if (h.bad || h.nonzero != nassigned || h.ndistinct == 0 || h.ndistinct > nassigned || h.ndistinct > s->lb_n)
+         return tally_library_fail("sort", l, h, n, nkeyed, nassigned, s->lb_n);
+      const size_t nd = h.ndistinct;
+      if (ws_grow(&s->ws, &s->cap_tl_tab, nd, {{s->tl_tab, nd * sizeof(seeqdev_tally_t)}})) return -1;
+      a.nd = h.ndistinct;
+      a.pos = (uint32_t *)a.dst;                           /* (4 bytes per head in the 8 bytes per span the last pass left free) */
+      a.tab = (uint4 *)s->tl_tab;
+      a.cap_tab = cap_u32(s->cap_tl_tab);
+      hipLaunchKernelGGL(k_tally_rle_apply, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
+      hipLaunchKernelGGL(k_tally_table, dim3((unsigned)((nd + SEEQ_TILE_WG - 1) / SEEQ_TILE_WG)), dim3(SEEQ_TILE_WG), 0, st, a);
+      if (counters_copy(s, s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt))) return -1;
+   }
+   if (s->tm_tl.end(s->prof, st)) return -1;
+   HIP_TRY(hipStreamSynchronize(st), EIO);
+   s->tm_tl.read(s->prof);
+   if (nassigned) {
+      h = *s->h_tlcnt;
+      /* the counts of the table telescope to n - the first head's index: the ids that are 0 lie before it */
+      if (h.bad || (uint64_t)n - h.first != nassigned) return tally_library_fail("table", l, h, n, nkeyed, nassigned, s->lb_n);
+      s->tl_n = h.ndistinct;
+      counts->ndistinct = h.ndistinct;
+   }
+   tally_library_counts(counts, l);
+   counts->nlong = packed.nlong; counts->nforeign = packed.nforeign;
+   counts->passes = passes;
+   return 0;
+}
+
+static int tally_library_none(void)
+{
+   snprintf(g_last_error, sizeof g_last_error, "library tally: the context holds no library (seeqdevScanSetLibrary)");
+   errno = EINVAL;
+   return -1;
+}
+
+extern "C" int seeqdevScanTallyLibrary(seeqdev_scan_t *s, int source, const void *d_text, size_t nbytes, seeqdev_tally_library_counts_t *counts)
+{
+   seeqerr = 0;
+   if (!s || !counts || (source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS) || (!d_text && nbytes)) { errno = EINVAL; return -1; }
+   if (!s->lb_n) return tally_library_none();
+   const uint4 *rec;
+   const uint64_t *off;
+   uint64_t n;
+   if (tally_source(s, source, &d_text, &nbytes, &rec, &off, &n)) return -1;
+   if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
+   if (use_device(s->device)) return -1;
+   s->tl_n = 0;                                            /* (the table of the tally before, of either kind, is gone, whatever comes of this one) */
+   s->tm_tl.ms = 0.f;
+   return tally_library_run(s, rec, off, (uint32_t)n, d_text, nbytes, counts);
+}
+
+extern "C" int seeqdevScanTallyHoldLibrary(seeqdev_scan_t *s, int source, const void *d_text, size_t nbytes, seeqdev_tally_library_counts_t *counts)
+{
+   seeqerr = 0;
+   if (!s || !counts || (source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS) || (!d_text && nbytes)) { errno = EINVAL; return -1; }
+   if (!s->lb_n) return tally_library_none();
+   const uint4 *rec;
+   const uint64_t *off;
+   uint64_t n;
+   if (tally_source(s, source, &d_text, &nbytes, &rec, &off, &n)) return -1;
+   if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
+   if (use_device(s->device)) return -1;
+   s->th_done = false;                                     /* (the column of the hold before is gone, whatever comes of this one) */
+   s->th_n = 0;
+   s->th_key_bits = 0;
+   seeqdev_tally_hold_counts_t held;
+   if (tally_hold_run(s, rec, off, (uint32_t)n, false, d_text, nbytes, &held)) return -1;
+   memset(counts, 0, sizeof *counts);
+   counts->nspans = n;
+   counts->key_bits = tally_lib_bitlen(s->lb_n);
+   counts->nlong = held.nlong; counts->nforeign = held.nforeign;
+   TallyLibCnt l = {};
+   if (held.nheld) {
+      /* the miss indices go where the plain tally's second key array lies: the scratch a following grouped call allocates anyway */
+      if (tally_ws_keys(s, (size_t)n)) return -1;
+      if ((size_t)n > s->cap_tl || (size_t)n > s->cap_th) {
+         snprintf(g_last_error, sizeof g_last_error, "library hold: %llu records, arrays for %zu and %zu", (unsigned long long)n, s->cap_th, s->cap_tl);
+         errno = EIO;
+         return -1;
+      }
+      if (tally_library_assign(s, s->th_key, (uint32_t *)s->tl_key1, (uint32_t)n, held.nheld, &l)) return -1;
+   }
+   tally_library_counts(counts, l);
+   if (counts->nexact + counts->ncorrected + counts->nambiguous + counts->nunknown + counts->nlong + counts->nforeign != n)
+      return tally_library_fail("hold", l, TallyCnt{}, (uint32_t)n, held.nheld, counts->nassigned, s->lb_n);
+   s->th_n = (size_t)n;
+   s->th_key_bits = counts->key_bits;
+   s->th_done = true;
+   return 0;
+}
+
+#endif

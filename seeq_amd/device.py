@@ -518,6 +518,51 @@ class Scanner:
         _check(self._lib.seeqdevScanLastTallyGroupedMs(self._h, C.byref(ms)))
         return float(ms.value)
 
+    # ---- counting against a known library (include/seeq_amd.h: seeqdevScanSetLibrary / seeqdevScanTallyLibrary / seeqdevScanTallyHoldLibrary) ----
+    def set_library(self, sequences, max_mismatch=1):
+        """Give this Scanner a library of known sequences -- guides, a barcode whitelist: str or bytes of at most 31 bases ACGTU each, or
+        an integer array of tally keys.  Entry i has the id i + 1.  max_mismatch 1: a span one substitution away from exactly one entry
+        counts for it; 0: exact only.  The library stays with the Scanner until the next set_library or clear_library; an empty one
+        clears it.  ValueError for a sequence that has no key, SeeqDeviceError for a duplicate."""
+        if isinstance(sequences, np.ndarray):
+            keys = np.ascontiguousarray(sequences, dtype=np.uint64)
+        else:
+            keys = np.array([q if isinstance(q, (int, np.integer)) else tally_key(q) for q in sequences], dtype=np.uint64)
+        _check(self._lib.seeqdevScanSetLibrary(self._h, keys.ctypes.data if len(keys) else None, len(keys), int(max_mismatch)))
+
+    def clear_library(self):
+        _check(self._lib.seeqdevScanSetLibrary(self._h, None, 0, 0))
+
+    @staticmethod
+    def _library_counts(cnt):
+        return {name: int(getattr(cnt, name)) for name, _ in _capi.seeqdev_tally_library_counts_t._fields_}
+
+    def tally_library(self, t=None, source="inserts", copy=True):
+        """One count per library entry seen among the spans of `source` ("inserts" or "hits", t as in tally()), assigned and counted on
+        the device: a span is exact (its sequence is an entry), corrected (one substitution away from exactly one entry, under
+        max_mismatch 1), ambiguous (from two or more), unknown, long or foreign.  -> dict: nspans, nassigned, nexact, ncorrected,
+        nambiguous, nunknown, nlong, nforeign, ndistinct, key_bits, passes; copy adds ids and counts, uint64 arrays in ascending id
+        order, entries without a read absent (library_counts makes the dense vector).  The table is the Scanner's tally table
+        (tally_device_ptr / tally_table, `key` = id), replaced by the next tally of either kind."""
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS}.get(source, source)
+        cnt = _capi.seeqdev_tally_library_counts_t()
+        _check(self._lib.seeqdevScanTallyLibrary(self._h, src, *self._text_args(t), C.byref(cnt)))
+        res = self._library_counts(cnt)
+        if copy:
+            tab = self.tally_table(res["ndistinct"])
+            res["ids"] = np.ascontiguousarray(tab["key"])
+            res["counts"] = np.ascontiguousarray(tab["count"])
+        return res
+
+    def tally_hold_library(self, t=None, source="inserts"):
+        """tally_hold ("inserts" or "hits") with the held keys assigned to the library: the group of a line is its entry's id, or none.
+        A following tally_grouped has one group per library entry seen, erroneous copies folded into their entry.  -> the dict of
+        tally_library (ndistinct and passes 0)."""
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX}.get(source, source)
+        cnt = _capi.seeqdev_tally_library_counts_t()
+        _check(self._lib.seeqdevScanTallyHoldLibrary(self._h, src, *self._text_args(t), C.byref(cnt)))
+        return self._library_counts(cnt)
+
     # ---- several patterns, one text (include/seeq_amd.h: seeqdevScanRunMulti / seeqdevScanHostMulti) ----
     def _multi(self, patterns, call, want, copy=True):
         n = len(patterns)
@@ -635,6 +680,17 @@ def tally_lookup(result, sequences):
         at = np.minimum(np.searchsorted(keys, want), len(keys) - 1)
         hit = keys[at] == want
         out[hit] = counts[at[hit]]
+    return out
+
+
+def library_counts(result, n):
+    """The dense count vector of a library of n entries from a tally_library() result (copy=True): uint64[n], entry i the count of
+    id i + 1, 0 for an entry without a read."""
+    ids, counts = np.asarray(result["ids"], dtype=np.uint64), np.asarray(result["counts"], dtype=np.uint64)
+    if len(ids) and (int(ids.min()) < 1 or int(ids.max()) > n):
+        raise ValueError("an id outside 1 .. %d: the result is not that of a library of %d entries" % (n, n))
+    out = np.zeros(n, dtype=np.uint64)
+    out[ids.astype(np.int64) - 1] = counts
     return out
 
 
