@@ -521,6 +521,57 @@ int seeqdevScanCopyTallyGroups(seeqdev_scan_t * scan, seeqdev_tally_group_t * ho
  * on; 0 otherwise, and when there was no span). */
 int seeqdevScanLastTallyGroupedMs(const seeqdev_scan_t * scan, float * ms);
 
+/* COLLAPSING UMI ERRORS IN THE GROUPED TALLY.  A UMI is random: it has no library to be counted against, so a group's ndistinct counts
+ * every sequencing error in a UMI as a molecule of its own.  seeqdevScanTallyCollapse stands behind seeqdevScanTallyGrouped and says, ON
+ * THE DEVICE (seeq_tally_collapse.h), per pair of the pair table whether it is a molecule of its own or an erroneous copy of another pair
+ * of its group, and per group how many molecules remain.  Pair i is (g_i, m_i, c_i), m_i a tally key of length L_i:
+ *   neighbour                the library's: another base at one position, the same length; a member of length 0 has none.
+ *   precedes                 pair j precedes pair i iff c_j > c_i, or c_j == c_i and m_j < m_i: within a group a strict total order.
+ *   candidate                of i: a pair j of the same group whose member is a neighbour of m_i, that precedes i and, under
+ *                            SEEQDEV_COLLAPSE_DIRECTIONAL, has c_j >= 2 c_i - 1 (evaluated without wrap-around);
+ *                            SEEQDEV_COLLAPSE_ANY drops the count threshold.
+ *   parent                   i has no candidate: a ROOT, parent[i] = i.  Else ABSORBED, parent[i] = the candidate that precedes all the
+ *                            others (the highest count, then the smallest member).  A parent precedes its child: the parents form a
+ *                            forest.  A parent may itself be absorbed (100 - 10 - 1): THE DEVICE DOES NOT FOLLOW CHAINS, a caller who
+ *                            wants family sizes does (seeq_amd.device.collapse_fold).  Of two neighbours with tied counts the smaller
+ *                            member is the root: the directional rule with a deterministic tie-break, which can differ from a
+ *                            breadth-first network in chains of tied pairs.
+ *   THE PARENTS              one uint32_t per entry of the pair table, an index into it.
+ *   THE COLLAPSE ROWS        one seeqdev_tally_collapse_t per row of the group table, row r for group row r: nroots = its molecules,
+ *                            nabsorbed = its pairs that are no root, absorbed_reads = the sum of their counts;
+ *                            nroots + nabsorbed == ndistinct of the group's row, and nroots >= 1.
+ * Synchronous.  EINVAL, before any device call: a NULL scan or counts, an unknown rule, a context without a completed grouped call (one
+ * that paired nothing is completed: the collapse of it is a valid empty result -- npairs, ngroups and every number 0, nothing launched).
+ * The collapse reads the pair and group tables and writes arrays of its own: both tables, the held column, the plain tally's table, the
+ * inserts result, the record arrays, the fetch state and the library are afterwards what they were.  Its result --
+ * seeqdevScanTallyParentsDevice / seeqdevScanCopyTallyParents, seeqdevScanTallyCollapseDevice / seeqdevScanCopyTallyCollapse -- is valid
+ * until the context's next grouped call (which clears it), the next collapse or seeqdevScanFree.  EIO: an internal inconsistency (the
+ * message names the numbers; the counts are filled in).
+ * Device memory of its own: 16 bytes per pair (parent, two prefixes), 16 per group, 12 per tile of 1 024 pairs, 24 per 64 pairs and 16
+ * per 256 groups.  (The reference counts nothing: an addition of this boundary.) */
+#define SEEQDEV_COLLAPSE_DIRECTIONAL 0
+#define SEEQDEV_COLLAPSE_ANY         1
+
+typedef struct {
+   uint32_t nroots, nabsorbed;
+   uint64_t absorbed_reads;
+} seeqdev_tally_collapse_t;   /* 16 bytes, row r belongs to group-table row r */
+
+typedef struct {
+   uint64_t npairs, ngroups;                    /* of the grouped call */
+   uint64_t nroots, nabsorbed, absorbed_reads;
+   uint32_t rule, max_len;                      /* the rule applied; the grouped call's largest paired member length */
+} seeqdev_tally_collapse_counts_t;   /* 48 bytes */
+
+int seeqdevScanTallyCollapse(seeqdev_scan_t * scan, int rule, seeqdev_tally_collapse_counts_t * counts);
+const uint32_t * seeqdevScanTallyParentsDevice(const seeqdev_scan_t * scan);
+const seeqdev_tally_collapse_t * seeqdevScanTallyCollapseDevice(const seeqdev_scan_t * scan);
+int seeqdevScanCopyTallyParents (seeqdev_scan_t * scan, uint32_t * host_out, size_t first, size_t n);
+int seeqdevScanCopyTallyCollapse(seeqdev_scan_t * scan, seeqdev_tally_collapse_t * host_out, size_t first, size_t n);
+/* Device time (ms) of the last collapse -- its launches and its counters copy, between two HIP events on the context's stream (profiling
+ * on; 0 otherwise, and when there was no pair). */
+int seeqdevScanLastTallyCollapseMs(const seeqdev_scan_t * scan, float * ms);
+
 /* COUNTING AGAINST A KNOWN LIBRARY: EXACT OR ONE MISMATCH.  The sequences of a screen or a barcode run are known in advance -- a guide
  * library, a whitelist -- and what is asked for is one count per library ENTRY, a read with one sequencing error counted for the entry it
  * came from.  seeqdevScanTally counts distinct OBSERVED sequences: every erroneous copy is a row of its own.  With a library set on the

@@ -108,6 +108,18 @@ class seeqdev_tally_grouped_counts_t(C.Structure):
                 ("npairs", C.c_uint64), ("ngroups", C.c_uint64), ("max_len", C.c_uint32), ("passes", C.c_uint32)]
 
 
+SEEQDEV_COLLAPSE_DIRECTIONAL, SEEQDEV_COLLAPSE_ANY = 0, 1
+
+
+class seeqdev_tally_collapse_t(C.Structure):
+    _fields_ = [("nroots", C.c_uint32), ("nabsorbed", C.c_uint32), ("absorbed_reads", C.c_uint64)]
+
+
+class seeqdev_tally_collapse_counts_t(C.Structure):
+    _fields_ = [("npairs", C.c_uint64), ("ngroups", C.c_uint64), ("nroots", C.c_uint64), ("nabsorbed", C.c_uint64), ("absorbed_reads", C.c_uint64),
+                ("rule", C.c_uint32), ("max_len", C.c_uint32)]
+
+
 class seeqdev_tally_library_counts_t(C.Structure):
     _fields_ = [("nspans", C.c_uint64), ("nassigned", C.c_uint64), ("nexact", C.c_uint64), ("ncorrected", C.c_uint64), ("nambiguous", C.c_uint64),
                 ("nunknown", C.c_uint64), ("nlong", C.c_uint64), ("nforeign", C.c_uint64), ("ndistinct", C.c_uint64), ("key_bits", C.c_uint32),
@@ -136,6 +148,8 @@ EXPORTS = [
     "seeqdevScanTally", "seeqdevScanTallyDevice", "seeqdevScanCopyTally", "seeqdevScanLastTallyMs", "seeqdevTallyKey", "seeqdevTallyDecode",
     "seeqdevScanTallyHold", "seeqdevScanTallyGrouped", "seeqdevScanTallyPairsDevice", "seeqdevScanTallyGroupsDevice", "seeqdevScanCopyTallyPairs",
     "seeqdevScanCopyTallyGroups", "seeqdevScanLastTallyGroupedMs",
+    "seeqdevScanTallyCollapse", "seeqdevScanTallyParentsDevice", "seeqdevScanTallyCollapseDevice", "seeqdevScanCopyTallyParents",
+    "seeqdevScanCopyTallyCollapse", "seeqdevScanLastTallyCollapseMs",
     "seeqdevScanSetLibrary", "seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary",
     "seeqdevScanLastRuns", "seeqdevScanFallback", "seeqdevScanLastPlan",
 ]
@@ -323,6 +337,16 @@ def lib():
         getattr(L, name).restype = C.c_int
     L.seeqdevScanLastTallyGroupedMs.argtypes = [C.c_void_p, P(C.c_float)]
     L.seeqdevScanLastTallyGroupedMs.restype = C.c_int
+    L.seeqdevScanTallyCollapse.argtypes = [C.c_void_p, C.c_int, P(seeqdev_tally_collapse_counts_t)]
+    L.seeqdevScanTallyCollapse.restype = C.c_int
+    for name in ("seeqdevScanTallyParentsDevice", "seeqdevScanTallyCollapseDevice"):
+        getattr(L, name).argtypes = [C.c_void_p]
+        getattr(L, name).restype = C.c_void_p
+    for name in ("seeqdevScanCopyTallyParents", "seeqdevScanCopyTallyCollapse"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        getattr(L, name).restype = C.c_int
+    L.seeqdevScanLastTallyCollapseMs.argtypes = [C.c_void_p, P(C.c_float)]
+    L.seeqdevScanLastTallyCollapseMs.restype = C.c_int
     L.seeqdevScanSetLibrary.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     L.seeqdevScanSetLibrary.restype = C.c_int
     for name in ("seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary"):

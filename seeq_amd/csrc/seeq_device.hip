@@ -23,7 +23,7 @@
  * Here: plumbing, pattern handle, scan context, the segment and packed drivers, the scan
  * entries.  The side entries are included where they belong in that order: seeq_synth.h,
  * seeq_text_alloc.h, seeq_multi_host.h, seeq_demux_host.h, seeq_strand_host.h, seeq_insert_host.h,
- * seeq_tally_host.h, seeq_tally_group_host.h, seeq_tally_library_host.h, seeq_string.h.
+ * seeq_tally_host.h, seeq_tally_group_host.h, seeq_tally_library_host.h, seeq_tally_collapse_host.h, seeq_string.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -113,7 +113,10 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_tally.h"
 #include "seeq_tally_group.h"
 #include "seeq_tally_library.h"
+#include "seeq_tally_collapse.h"
 static_assert(sizeof(seeqdev_tally_pair_t) == 24 && sizeof(seeqdev_tally_group_t) == 24, "pair and group entries are written as three 64-bit words");
+static_assert(sizeof(seeqdev_tally_collapse_t) == sizeof(uint4) && SEEQ_COLLAPSE_DIRECTIONAL == SEEQDEV_COLLAPSE_DIRECTIONAL && SEEQ_COLLAPSE_ANY == SEEQDEV_COLLAPSE_ANY,
+              "collapse rows are written as uint4");
 static_assert(sizeof(seeqdev_demux_t) == 16 && sizeof(seeqdev_hit_t) == sizeof(uint4), "demux records are written as uint4");
 static_assert(sizeof(seeqdev_insert_t) == sizeof(uint4), "insert records are written as uint4");
 static_assert(sizeof(seeqdev_tally_t) == sizeof(uint4) && SEEQ_TALLY_LEN_MAX == SEEQDEV_TALLY_MAX_LEN, "tally entries are written as uint4");
@@ -576,6 +579,15 @@ struct seeqdev_scan {
    uint32_t *lb_sum; size_t cap_lb_sum;                   /* per tile of spans: misses, exact */
    uint4    *lb_nstat; size_t cap_lb_near;                /* per workgroup of the near pass: corrected, ambiguous, unknown, bad */
    TallyLibCnt *d_lbcnt, *h_lbcnt;                        /* h_ pinned */
+   /* seeqdevScanTallyCollapse (seeq_tally_collapse.h): reads the two tables of the last grouped call, writes arrays of its own; its result
+      (tc_parent: tc_np entries, tc_groups: tc_ng rows) is valid until the next grouped call or the next collapse */
+   bool      tg_done;                                     /* a grouped call has completed: tg_np pairs in tg_ng groups (none included) are a result */
+   uint64_t  tg_npaired; uint32_t tg_max_len;             /* its paired spans and its largest paired member length */
+   uint32_t *tc_parent, *tc_proot; uint64_t *tc_pread; uint32_t *tc_rsum; uint64_t *tc_qsum; CollapseWg *tc_wst; size_t cap_tc;      /* per pair: parent, the two prefixes; per tile: their sums; per 64 pairs: the parents' numbers */
+   seeqdev_tally_collapse_t *tc_groups; uint4 *tc_gst; size_t cap_tc_groups;      /* per group: its row; per 256 groups: their numbers */
+   CollapseCnt *d_tccnt, *h_tccnt;                        /* h_ pinned */
+   size_t    tc_np, tc_ng;                                /* entries of the last collapse's two arrays */
+   EventPair tm_tc;                                       /* profiling: around the collapse's launches and its counters copy */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -698,7 +710,7 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
 {
    if (!s) return;
    (void)use_device(s->device);
-   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl, &s->tm_tg})
+   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl, &s->tm_tg, &s->tm_tc})
       if (t->made) { (void)hipEventDestroy(t->ev[0]); (void)hipEventDestroy(t->ev[1]); }
    (void)hipStreamSynchronize(s->stream);
    ws_free_all(&s->ws);
@@ -1870,6 +1882,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 #include "seeq_tally_host.h"
 #include "seeq_tally_group_host.h"
 #include "seeq_tally_library_host.h"
+#include "seeq_tally_collapse_host.h"
 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {

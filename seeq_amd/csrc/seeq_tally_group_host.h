@@ -222,8 +222,13 @@ extern "C" int seeqdevScanTallyGrouped(seeqdev_scan_t *s, int source, const void
    if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
    if (use_device(s->device)) return -1;
    s->tg_np = s->tg_ng = 0;                                /* (the tables of the call before are gone, whatever comes of this one) */
+   s->tg_done = false;
+   s->tc_np = s->tc_ng = 0;                                /* (... and with them what a collapse made of them: seeq_tally_collapse_host.h) */
    s->tm_tg.ms = 0.f;
-   return tally_grouped_run(s, rec, off, (uint32_t)n, d_text, nbytes, counts);
+   if (tally_grouped_run(s, rec, off, (uint32_t)n, d_text, nbytes, counts)) return -1;
+   s->tg_npaired = counts->npaired; s->tg_max_len = counts->max_len;
+   s->tg_done = true;                                      /* (a call that paired nothing included) */
+   return 0;
 }
 
 extern "C" const seeqdev_tally_pair_t *seeqdevScanTallyPairsDevice(const seeqdev_scan_t *s) { return s ? s->tg_pairs : NULL; }

@@ -518,6 +518,50 @@ class Scanner:
         _check(self._lib.seeqdevScanLastTallyGroupedMs(self._h, C.byref(ms)))
         return float(ms.value)
 
+    # ---- collapsing UMI errors behind the grouped tally (include/seeq_amd.h: seeqdevScanTallyCollapse) ----
+    def tally_collapse(self, rule="directional", copy=True):
+        """Per pair of the last tally_grouped's pair table: a molecule of its own (a root, its own parent) or an erroneous copy, one
+        substitution away, of another pair of its group (its parent's index) -- decided on the device.  rule "directional": a parent
+        has at least 2 c - 1 reads for a child of c; "any": every neighbour that precedes (higher count, then smaller member).
+        -> dict: npairs, ngroups, nroots, nabsorbed, absorbed_reads, rule, max_len; copy adds parent (uint32 per pair) and groups
+        (TALLY_COLLAPSE_DTYPE, row r for row r of the group table: nroots, nabsorbed, absorbed_reads).  Chains are not followed:
+        collapse_fold does that.  copy=False leaves both on the device (tally_parents_device_ptr / tally_parents_table,
+        tally_collapse_device_ptr / tally_collapse_table)."""
+        r = {"directional": _capi.SEEQDEV_COLLAPSE_DIRECTIONAL, "any": _capi.SEEQDEV_COLLAPSE_ANY}.get(rule, rule)
+        cnt = _capi.seeqdev_tally_collapse_counts_t()
+        _check(self._lib.seeqdevScanTallyCollapse(self._h, r, C.byref(cnt)))
+        res = {name: int(getattr(cnt, name)) for name, _ in _capi.seeqdev_tally_collapse_counts_t._fields_}
+        if copy:
+            res["parent"] = self.tally_parents_table(res["npairs"])
+            res["groups"] = self.tally_collapse_table(res["ngroups"])
+        return res
+
+    def tally_parents_table(self, n, first=0):
+        """Copy entries [first, first + n) of the last collapse's parents to the host -> uint32 array (indices into the pair table)."""
+        out = np.zeros(n, dtype=np.uint32)
+        _check(self._lib.seeqdevScanCopyTallyParents(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def tally_collapse_table(self, n, first=0):
+        """Copy rows [first, first + n) of the last collapse's group rows to the host -> structured array of TALLY_COLLAPSE_DTYPE."""
+        out = np.zeros(n, dtype=TALLY_COLLAPSE_DTYPE)
+        _check(self._lib.seeqdevScanCopyTallyCollapse(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def tally_parents_device_ptr(self):
+        """Device address of the last collapse's parents (uint32 per pair; valid until this Scanner's next grouped tally or collapse)."""
+        return self._lib.seeqdevScanTallyParentsDevice(self._h)
+
+    def tally_collapse_device_ptr(self):
+        """Device address of the last collapse's group rows (seeqdev_tally_collapse_t; valid until the next grouped tally or collapse)."""
+        return self._lib.seeqdevScanTallyCollapseDevice(self._h)
+
+    def last_tally_collapse_ms(self):
+        """Device time of the last collapse (its launches and its counters copy; profiling on), 0 when not measured."""
+        ms = C.c_float(0)
+        _check(self._lib.seeqdevScanLastTallyCollapseMs(self._h, C.byref(ms)))
+        return float(ms.value)
+
     # ---- counting against a known library (include/seeq_amd.h: seeqdevScanSetLibrary / seeqdevScanTallyLibrary / seeqdevScanTallyHoldLibrary) ----
     def set_library(self, sequences, max_mismatch=1):
         """Give this Scanner a library of known sequences -- guides, a barcode whitelist: str or bytes of at most 31 bases ACGTU each, or
@@ -709,6 +753,33 @@ def tally_members(result, group):
         return pairs[:0]
     first = int(groups["first"][at])
     return pairs[first:first + int(groups["ndistinct"][at])]
+
+
+# One row of seeqdevScanTallyCollapse's group rows (seeq_amd.h: seeqdev_tally_collapse_t, 16 bytes).
+TALLY_COLLAPSE_DTYPE = np.dtype([("nroots", "<u4"), ("nabsorbed", "<u4"), ("absorbed_reads", "<u8")])
+
+
+def collapse_fold(pairs, parent):
+    """Follow the parents of a tally_collapse() result to their roots, on the host: -> (root, folded).  root[i] (uint32) is the index of
+    the root of pair i's family (i itself for a root); folded[i] (uint64) is, for a root, the reads of its whole family -- its own count
+    and those of every pair absorbed into it, directly or through a chain -- and 0 for a pair that is no root.  pairs: the pair table
+    (TALLY_PAIR_DTYPE) the parents belong to.  Pointer doubling: O(log depth) gathers.  ValueError: parent and pairs differ in length, a
+    parent index lies outside the table, or the parents do not form a forest."""
+    parent = np.asarray(parent)
+    n = len(pairs)
+    if parent.ndim != 1 or len(parent) != n:
+        raise ValueError("%d parents for %d pairs" % (parent.size, n))
+    up = parent.astype(np.int64)
+    if n and (int(up.min()) < 0 or int(up.max()) >= n):
+        raise ValueError("a parent index outside the %d pairs of the table" % n)
+    root = up
+    for _ in range(max(n, 1).bit_length() + 1):             # (a chain of n pairs is done after ceil(log2 n) doublings)
+        root = root[root]
+    if not np.array_equal(up[root], root):                  # (what a pair ends on is its own parent, or it went round a cycle)
+        raise ValueError("the parents do not form a forest (a cycle)")
+    folded = np.zeros(n, dtype=np.uint64)
+    np.add.at(folded, root, np.asarray(pairs["count"], dtype=np.uint64))
+    return root.astype(np.uint32), folded
 
 
 # One record of seeqdevScanRunDemux (seeq_amd.h: seeqdev_demux_t, 16 bytes).
