@@ -406,7 +406,7 @@ int seeqdevScanLastInsertsMs(const seeqdev_scan_t * scan, float * join_ms);
  * that reaches beyond nbytes (checked before any byte of it is loaded; the context stays usable), or an internal inconsistency.
  * E2BIG: more than 2^32 - 1 spans.
  * Device memory of its own (allocated by a context's first tally, freed with it): 17 bytes per span (two 8-byte key arrays, a
- * 1 KiB digit matrix per tile of 1 024 spans) plus 25 bytes per tile, and 16 bytes per distinct key.
+ * 1 KiB digit matrix per tile of 1 024 spans) plus 41 bytes per tile, and 16 bytes per distinct key.
  * seeqdevTallyKey / seeqdevTallyDecode: the rule's two directions on the host, no GPU needed.  Key: -1 / EINVAL for a long or foreign
  * sequence.  Decode: writes the bases in upper case by code (A C T G) and a terminating 0, returns L; -1 / EINVAL for a value that
  * is no key (0, bit 63 set, a leading 1 at an odd bit).  (The reference counts nothing: an addition of this boundary.) */

@@ -551,7 +551,7 @@ struct seeqdev_scan {
    EventPair tm_ins;                                      /* profiling: around the join's launches */
    bool      ins_done;                                    /* an inserts call has completed: ins_n records (none included) are a result */
    /* seeqdevScanTally (seeq_tally.h): allocated by the first tally; the table (tl_tab, tl_n) is valid until the next one */
-   uint64_t *tl_key0, *tl_key1; uint32_t *tl_mat, *tl_sum; uint4 *tl_stat; size_t cap_tl;      /* per span: the two key arrays; per tile: the digit matrix, the sums, the pack's numbers */
+   uint64_t *tl_key0, *tl_key1; uint32_t *tl_mat, *tl_sum, *tl_stat; size_t cap_tl;      /* per span: the two key arrays; per tile: the digit matrix, the sums, the pack's eight words */
    seeqdev_tally_t *tl_tab; size_t cap_tl_tab;            /* the table: one entry per distinct key */
    TallyCnt *d_tlcnt, *h_tlcnt;                           /* h_ pinned */
    size_t    tl_n;                                        /* entries of the last tally's table */

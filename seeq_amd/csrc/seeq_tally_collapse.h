@@ -91,30 +91,14 @@ SEEQ_ST_HD int collapse_segment(const uint64_t *gtab, uint64_t r, uint32_t np, u
    return ok;
 }
 
-/* pairs with a member below `key` among the pairs before `end`, searched from `first` on (a group's segment, ascending by member); at most
-   `probes` steps */
+/* pairs with a member below `key` among the pairs before `end`, searched from `first` on (a group's segment, ascending by member), and group
+   rows with a key below g among gtab's ng rows: tally_lower_bound over a column of a table, every third word; at most `probes` steps */
 SEEQ_ST_HD uint32_t collapse_lower_bound(const uint64_t *ptab, uint32_t first, uint32_t end, uint32_t probes, uint64_t key)
 {
-   uint32_t lo = first, hi = end;
-   for (uint32_t it = 0; it < probes && lo < hi; it++) {
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if (collapse_member(ptab, mid) < key) lo = mid + 1u;
-      else hi = mid;
-   }
-   return lo;
+   return tally_lower_bound(ptab + 1, 3u, first, end, probes, key);
 }
 
-/* group rows with a key below g among gtab's ng rows, ascending; at most `probes` steps */
-SEEQ_ST_HD uint32_t collapse_group_lower_bound(const uint64_t *gtab, uint32_t ng, uint32_t probes, uint64_t g)
-{
-   uint32_t lo = 0, hi = ng;
-   for (uint32_t it = 0; it < probes && lo < hi; it++) {
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if (gtab[3u * (uint64_t)mid] < g) lo = mid + 1u;
-      else hi = mid;
-   }
-   return lo;
-}
+SEEQ_ST_HD uint32_t collapse_group_lower_bound(const uint64_t *gtab, uint32_t ng, uint32_t probes, uint64_t g) { return tally_lower_bound(gtab, 3u, 0u, ng, probes, g); }
 
 /* THE TOP OF THE GROUP SEARCH, kept in LDS by k_collapse_parent: every stride-th group key (stride = tally_lib_stride(ng)), SEEQ_TLIB_TOP
    samples with the largest 64-bit value behind the last one: tally_lib_top_range over them gives the range of at most stride rows that
@@ -125,17 +109,12 @@ SEEQ_ST_HD uint64_t collapse_group_sample(const uint64_t *gtab, uint32_t ng, uin
    return at < ng ? gtab[3u * at] : ~0ull;
 }
 
-/* the lower bound by both levels: the samples, then at most `probes` = tally_lib_probes(stride) steps over the table */
+/* the group row by both levels: the samples, then at most `probes` = tally_lib_probes(stride) steps over the range they leave */
 SEEQ_ST_HD uint32_t collapse_group_lower_bound_top(const uint64_t *top, const uint64_t *gtab, uint32_t ng, uint32_t stride, uint32_t probes, uint64_t g)
 {
    uint32_t lo, hi;
    tally_lib_top_range(top, ng, stride, g, &lo, &hi);
-   for (uint32_t it = 0; it < probes && lo < hi; it++) {
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if (gtab[3u * (uint64_t)mid] < g) lo = mid + 1u;
-      else hi = mid;
-   }
-   return lo;
+   return tally_lower_bound(gtab, 3u, lo, hi, probes, g);
 }
 
 /* THE RULE: the parent of pair i < np (i itself: a root).  *bad is set when the tables contradict each other: the pair's group has no row,
@@ -237,12 +216,7 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_collapse_parent(CollapseArgs a
          c = collapse_count(a.ptab, i);
          uint32_t lo, hi;                                   /* the pair's group row: the same search in every lane of the half */
          tally_lib_top_range(s_top, a.ng, a.gstride, g, &lo, &hi);
-#pragma unroll 1
-         for (uint32_t it = 0; it < a.gprobes && lo < hi; it++) {
-            const uint32_t mid = lo + (hi - lo) / 2u;       /* (< hi <= ng) */
-            if (a.gtab[3u * (uint64_t)mid] < g) lo = mid + 1u;
-            else hi = mid;
-         }
+         lo = tally_lower_bound(a.gtab, 3u, lo, hi, a.gprobes, g);      /* (hi <= ng) */
          if (lo < a.ng && a.gtab[3u * (uint64_t)lo] == g && collapse_segment(a.gtab, lo, a.np, &first, &end) && i >= first && i < end) {
             len = tally_key_len(m);
          } else {
@@ -264,11 +238,7 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_collapse_parent(CollapseArgs a
          bool more = false;
 #pragma unroll
          for (int s = 0; s < 3; s++) {
-            if (lo[s] < hi[s]) {
-               const uint32_t mid = lo[s] + (hi[s] - lo[s]) / 2u;      /* (< hi <= end <= np) */
-               if (collapse_member(a.ptab, mid) < nb[s]) lo[s] = mid + 1u;
-               else hi[s] = mid;
-            }
+            tally_bound_step(a.ptab + 1, 3u, nb[s], &lo[s], &hi[s]);      /* (the members' column; mid < hi <= end <= np) */
             more |= lo[s] < hi[s];
          }
          if (__ballot(more) == 0ull) break;                 /* (no lane of the wave has a range left) */

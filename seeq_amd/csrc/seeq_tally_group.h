@@ -28,15 +28,14 @@
  *                minus its own.
  *
  *   k_tally_hold          one thread per held record, in the tiles of seeq_tiles.h: hold_line / hold_key AT THE RECORD'S OWN INDEX; span
- *                         bytes by the wide unaligned loads of k_tally_pack; per tile eight words {long, foreign, largest L, bad,
- *                         ambiguous, largest key's bits, 0, 0}.
- *   k_tally_group_top     one workgroup: the tiles' words -> the totals (after the hold and after the pair pack alike).
- *   k_tally_pair_pack     one thread per member span: the member key as k_tally_pack computes it, the tally_group_of search (at most
- *                         32 probes), g and m stored AT THE SPAN'S OWN INDEX in two key arrays; per tile {long, foreign, largest
- *                         paired L, bad, ungrouped, 0, 0, 0}.
- *   per pass of the sort  k_tally_pair_hist (the digit of the word the pass sorts by), the three scan launches of the digit matrix as
- *                         they are (k_tally_scan_reduce / _top / _apply of seeq_tally.h), k_tally_pair_scatter (k_tally_scatter's
- *                         ranks, both words moved).  Every pass takes its histogram from the arrays it permutes.
+ *                         bytes by tally_span_load; per tile the eight words of tally_tile_stat (seeq_tally.h) {long, foreign, largest L,
+ *                         bad, ambiguous, largest key's bits, 0, 0}.
+ *   k_tally_group_top     one workgroup: the tiles' words -> the totals (tally_stat_top; after the hold and after the pair pack alike).
+ *   k_tally_pair_pack     one thread per member span: the member key by tally_span_load, the tally_group_of search (at most 32 probes),
+ *                         g and m stored AT THE SPAN'S OWN INDEX in two key arrays; per tile {long, foreign, largest paired L, bad,
+ *                         ungrouped, 0, 0, 0}.
+ *   the sort              seeq_tally.h's, of two-word items: word 0 the member, word 1 the group; k_tally_pair_hist and
+ *                         k_tally_pair_scatter are its two-word instantiations.
  *   k_tally_pair_rle_reduce / _top / _apply    per tile: pair heads, group heads, nonzero items; one workgroup: the exclusive prefix of
  *                         BOTH head rows (tile_top scans one row: it is called once per row), the totals, the tiles' flags; the ordered
  *                         compaction: pair head j's index -> ppos[j]; group head r's index -> gpos[r] and its pair rank -> grank[r]
@@ -103,8 +102,6 @@ SEEQ_ST_HD int tally_is_group_head(uint64_t g, uint64_t pg, int first) { return 
 
 #if defined(__HIPCC__)
 
-#define SEEQ_TG_STAT 8                                      /* words per tile: {long, foreign, largest L, bad, ambiguous | ungrouped, key bits, sort flag, 0} */
-
 struct TallyGroupCnt {
    uint32_t nlong, nforeign;          /* spans without a key, by kind */
    uint32_t nthird;                   /* the hold: ambiguous demux records; the pair pack: ungrouped spans */
@@ -128,11 +125,8 @@ struct TallyGroupArgs {
    uint32_t       *hold_line;         /* [nh] the held column: k_tally_hold writes it, k_tally_pair_pack searches it */
    uint64_t       *hold_key;
    uint32_t        nh;
-   uint64_t       *msrc, *mdst;       /* [n] member words a kernel reads / a pass writes */
-   uint64_t       *gsrc, *gdst;       /* [n] group words */
-   uint32_t       *mat;               /* [256 * nt] digit-major, as TallyArgs.mat */
-   uint32_t        word, pass;        /* the word a pass sorts by (0 member, 1 group) and the digit of it */
-   uint32_t       *tstat;             /* [8 * nt] the tiles' words */
+   uint64_t       *msrc, *gsrc;       /* [n] member words, group words: the pair pack writes them, the sort leaves them here */
+   uint32_t       *tstat;             /* [8 * nt] the tiles' words (tally_tile_stat: the third count is ambiguous | ungrouped) */
    uint32_t       *rsum;              /* [3 * nt] per tile pair heads, group heads (k_tally_pair_rle_top: exclusive prefixes), nonzero items */
    uint32_t        np, ng;            /* entries of the two tables */
    uint32_t       *ppos;              /* [np] the pair heads' indices */
@@ -141,54 +135,6 @@ struct TallyGroupArgs {
    uint32_t        cap_ptab, cap_gtab;
    TallyGroupCnt  *cnt;
 };
-
-/* What the span [start, end) of the line at `off` is, and its key (0 unless SEEQ_TALLY_OK): k_tally_pack's loads -- the span's bytes in one
-   or two unaligned 16-byte loads where 16 / 32 bytes from its first one lie inside the text, byte by byte elsewhere; nothing of a long or
-   bad span. */
-__device__ __forceinline__ int tally_span_load(const uint8_t *text, uint64_t nbytes, uint64_t off, uint32_t start, uint32_t end, uint64_t *key, uint32_t *len)
-{
-   *key = 0u;
-   const int kind = tally_span_kind(nbytes, off, start, end, len);
-   if (kind != SEEQ_TALLY_OK) return kind;
-   const uint64_t p = off + start;
-   const uint32_t nvec = *len > 16u ? 2u : 1u;
-   if (*len == 0u) {
-      *key = 1u;
-   } else if (p + 16u * nvec <= nbytes) {
-      const fused_v4u v0 = *(const fused_v4u_unaligned *)(text + p);
-      fused_v4u v1 = {0u, 0u, 0u, 0u};
-      if (nvec == 2u) v1 = *(const fused_v4u_unaligned *)(text + p + 16);
-      const uint32_t w[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      *key = tally_key_of_words(w, *len);
-   } else {
-      *key = tally_key_of(text + p, *len);
-   }
-   return *key ? SEEQ_TALLY_OK : SEEQ_TALLY_FOREIGN;
-}
-
-/* A tile's words: three wave-uniform counts, three values of this lane (two maxima, a flag) -> tstat[8 * tile ..], by thread 0. */
-__device__ __forceinline__ void tally_group_tile_stat(uint32_t nlong, uint32_t nfor, uint32_t third, uint32_t maxl, uint32_t bits, uint32_t bad,
-                                                      uint32_t (&s_st)[6][SEEQ_TILE_WAVES], uint32_t *tstat)
-{
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   maxl = tally_wave_max(maxl);
-   bits = tally_wave_max(bits);
-   bad = __ballot(bad != 0u) != 0ull ? 1u : 0u;
-   if (lane == 0) { s_st[0][wave] = nlong; s_st[1][wave] = nfor; s_st[2][wave] = maxl; s_st[3][wave] = bad; s_st[4][wave] = third; s_st[5][wave] = bits; }
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      uint32_t t[SEEQ_TG_STAT] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-      for (int w = 0; w < SEEQ_TILE_WAVES; w++) {
-         t[0] += s_st[0][w]; t[1] += s_st[1][w]; t[4] += s_st[4][w];
-         t[2] = s_st[2][w] > t[2] ? s_st[2][w] : t[2];
-         t[5] = s_st[5][w] > t[5] ? s_st[5][w] : t[5];
-         t[3] |= s_st[3][w];
-      }
-      uint4 *out = (uint4 *)(tstat + (size_t)SEEQ_TG_STAT * blockIdx.x);
-      out[0] = make_uint4(t[0], t[1], t[2], t[3]);
-      out[1] = make_uint4(t[4], t[5], 0u, 0u);
-   }
-}
 
 __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_hold(TallyGroupArgs a)
 {
@@ -224,37 +170,18 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_hold(TallyGroupArgs a)
       nfor += (uint32_t)__popcll(__ballot(kind == SEEQ_TALLY_FOREIGN));
       namb += (uint32_t)__popcll(__ballot(amb));
    }
-   tally_group_tile_stat(nlong, nfor, namb, maxl, bits, bad, s_st, a.tstat);
+   tally_tile_stat(nlong, nfor, namb, maxl, bits, bad, s_st, a.tstat);
 }
 
-/* One workgroup: the tiles' words -> the totals (sums of words 0, 1, 4; maxima of 2, 5; word 3 or-ed). */
+/* One workgroup: the tiles' words -> the totals (after the hold and after the pair pack alike). */
 __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_group_top(TallyGroupArgs a)
 {
    __shared__ uint32_t s_wave[SEEQ_TILE_WAVES], s_st[3][SEEQ_TILE_WAVES];
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   uint32_t nlong = 0, nfor = 0, third = 0, maxl = 0, bits = 0, bad = 0;
-   for (uint32_t b0 = 0; b0 < a.nt; b0 += SEEQ_TILE_WG) {
-      const uint32_t i = b0 + threadIdx.x;
-      if (i < a.nt) {
-         const uint4 *t = (const uint4 *)(a.tstat + (size_t)SEEQ_TG_STAT * i);
-         const uint4 t0 = t[0], t1 = t[1];
-         nlong += t0.x; nfor += t0.y; maxl = t0.z > maxl ? t0.z : maxl; bad |= t0.w;
-         third += t1.x; bits = t1.y > bits ? t1.y : bits;
-      }
-   }
-   uint32_t tot_long, tot_for, tot_third;
-   block_excl_scan(nlong, &tot_long, s_wave);
-   block_excl_scan(nfor, &tot_for, s_wave);
-   block_excl_scan(third, &tot_third, s_wave);
-   maxl = tally_wave_max(maxl);
-   bits = tally_wave_max(bits);
-   bad = __ballot(bad != 0u) != 0ull ? 1u : 0u;
-   if (lane == 0) { s_st[0][wave] = maxl; s_st[1][wave] = bits; s_st[2][wave] = bad; }
-   __syncthreads();
+   uint32_t t[6];
+   tally_stat_top(a.tstat, a.nt, s_wave, s_st, t);
    if (threadIdx.x == 0) {
-      for (int w = 0; w < SEEQ_TILE_WAVES; w++) { maxl = s_st[0][w] > maxl ? s_st[0][w] : maxl; bits = s_st[1][w] > bits ? s_st[1][w] : bits; bad |= s_st[2][w]; }
-      a.cnt->nlong = tot_long; a.cnt->nforeign = tot_for; a.cnt->nthird = tot_third;
-      a.cnt->max_len = maxl; a.cnt->key_bits = bits; a.cnt->bad = bad;
+      a.cnt->nlong = t[0]; a.cnt->nforeign = t[1]; a.cnt->max_len = t[2]; a.cnt->bad = t[3];
+      a.cnt->nthird = t[4]; a.cnt->key_bits = t[5];
    }
 }
 
@@ -284,76 +211,7 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_pair_pack(TallyGroupArgs
       nfor += (uint32_t)__popcll(__ballot(kind == SEEQ_TALLY_FOREIGN));
       nung += (uint32_t)__popcll(__ballot(kind == SEEQ_TALLY_UNGROUPED));
    }
-   tally_group_tile_stat(nlong, nfor, nung, maxl, 0u, bad, s_st, a.tstat);
-}
-
-/* k_tally_hist over the word the pass sorts by */
-__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_pair_hist(TallyGroupArgs a)
-{
-   __shared__ uint32_t s_h[SEEQ_TALLY_RADIX];
-   const uint64_t *src = a.word ? a.gsrc : a.msrc;
-   s_h[threadIdx.x] = 0u;
-   __syncthreads();
-#pragma unroll
-   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
-      const uint64_t i = tile_index(k);
-      if (i < a.n) atomicAdd(&s_h[tally_digit(src[i], a.pass)], 1u);      /* (LDS) */
-   }
-   __syncthreads();
-   a.mat[(uint64_t)threadIdx.x * a.nt + blockIdx.x] = s_h[threadIdx.x];
-}
-
-/* k_tally_scatter with both words of an item moved: the ranks are its ranks (rounds, waves, lanes in ascending index: stable) */
-__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_pair_scatter(TallyGroupArgs a)
-{
-   __shared__ uint32_t s_cnt[SEEQ_TILE_ITEMS * SEEQ_TILE_WAVES][SEEQ_TALLY_RADIX];      /* [round][wave] per digit: count, then destination */
-   __shared__ uint32_t s_bad;
-   constexpr int ROWS = SEEQ_TILE_ITEMS * SEEQ_TILE_WAVES;
-   const int wave = threadIdx.x >> 6;
-#pragma unroll
-   for (int r = 0; r < ROWS; r++) s_cnt[r][threadIdx.x] = 0u;
-   if (threadIdx.x == 0) s_bad = 0u;
-   __syncthreads();
-   uint64_t m[SEEQ_TILE_ITEMS], g[SEEQ_TILE_ITEMS];
-   uint32_t dg[SEEQ_TILE_ITEMS], within[SEEQ_TILE_ITEMS];
-#pragma unroll
-   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
-      const uint64_t i = tile_index(k);
-      const bool act = i < a.n;
-      m[k] = act ? a.msrc[i] : 0u;
-      g[k] = act ? a.gsrc[i] : 0u;
-      dg[k] = tally_digit(a.word ? g[k] : m[k], a.pass);
-      uint64_t same = __ballot(act);                        /* the wave's lanes that hold an item of this lane's digit */
-#pragma unroll
-      for (int b = 0; b < 8; b++) {
-         const bool bit = (dg[k] >> b) & 1u;
-         const uint64_t bal = __ballot(bit);
-         same &= bit ? bal : ~bal;
-      }
-      within[k] = __builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0u));
-      if (act && within[k] == 0u) s_cnt[k * SEEQ_TILE_WAVES + wave][dg[k]] = (uint32_t)__popcll(same);
-   }
-   __syncthreads();
-   {
-      uint32_t run = a.mat[(uint64_t)threadIdx.x * a.nt + blockIdx.x];      /* where the tile's first item of digit tid goes */
-#pragma unroll
-      for (int r = 0; r < ROWS; r++) {
-         const uint32_t c = s_cnt[r][threadIdx.x];
-         s_cnt[r][threadIdx.x] = run;
-         run += c;
-      }
-   }
-   __syncthreads();
-#pragma unroll
-   for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
-      const uint64_t i = tile_index(k);
-      if (i >= a.n) continue;
-      const uint32_t j = s_cnt[k * SEEQ_TILE_WAVES + wave][dg[k]] + within[k];
-      if (j < a.n) { a.mdst[j] = m[k]; a.gdst[j] = g[k]; }
-      else s_bad = 1u;
-   }
-   __syncthreads();
-   if (threadIdx.x == 0 && s_bad) a.tstat[(size_t)SEEQ_TG_STAT * blockIdx.x + 6] = 2u;
+   tally_tile_stat(nlong, nfor, nung, maxl, 0u, bad, s_st, a.tstat);
 }
 
 /* the two head predicates of sorted item i < n (its predecessor is read from the arrays: it may lie in another tile) */
@@ -392,7 +250,7 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_pair_rle_top(TallyGroupA
    uint32_t tot[3], gtot[1], bad = 0;
    tile_top(a.rsum, a.nt, s_wave, tot);                     /* (rows 1 and 2 are read as the reduce left them ...) */
    tile_top(a.rsum + a.nt, a.nt, s_wave, gtot);             /* (... before row 1 is scanned: every entry by the thread that read it) */
-   for (uint32_t i = threadIdx.x; i < a.nt; i += SEEQ_TILE_WG) bad |= a.tstat[(size_t)SEEQ_TG_STAT * i + 6];
+   for (uint32_t i = threadIdx.x; i < a.nt; i += SEEQ_TILE_WG) bad |= a.tstat[(size_t)SEEQ_TALLY_STAT * i + SEEQ_TALLY_STAT_FLAG];
    bad = __ballot(bad != 0u) != 0ull ? 2u : 0u;
    if (lane == 0) s_bad[wave] = bad;
    __syncthreads();

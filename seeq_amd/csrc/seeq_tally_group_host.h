@@ -40,7 +40,7 @@ static int tally_hold_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off
    const size_t nt = (size_t)tally_tiles(n);
    if (tally_group_ws_cnt(s)) return -1;
    if (ws_grow(&s->ws, &s->cap_th, n, {{s->th_line, n * sizeof(uint32_t)}, {s->th_key, n * sizeof(uint64_t)},
-                                       {s->th_stat, nt * SEEQ_TG_STAT * sizeof(uint32_t)}})) return -1;
+                                       {s->th_stat, nt * SEEQ_TALLY_STAT * sizeof(uint32_t)}})) return -1;
    TallyGroupArgs a;
    memset(&a, 0, sizeof a);
    a.rec = rec; a.off = off; a.n = n; a.nt = (uint32_t)nt;
@@ -70,13 +70,13 @@ static int tally_hold_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off
 
 extern "C" int seeqdevScanTallyHold(seeqdev_scan_t *s, int source, const void *d_text, size_t nbytes, seeqdev_tally_hold_counts_t *counts)
 {
-   seeqerr = 0;
    const bool demux = source == SEEQDEV_TALLY_DEMUX;
-   if (!s || !counts || (source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS && !demux) || (!demux && !d_text && nbytes)) { errno = EINVAL; return -1; }
    const uint4 *rec;
    const uint64_t *off = NULL;
    uint64_t n;
    if (demux) {
+      seeqerr = 0;
+      if (!s || !counts) { errno = EINVAL; return -1; }
       /* what seeqdevScanDemuxDevice serves: valid until the context's next scan -- a demux leaves nothing to fetch (scan_forget), a plain or
          packed scan after it leaves its pattern */
       if (!s->dm_done || s->pat || s->ran) {
@@ -86,11 +86,11 @@ extern "C" int seeqdevScanTallyHold(seeqdev_scan_t *s, int source, const void *d
       }
       rec = s->dm_out; n = s->dm_nrec;
       d_text = NULL; nbytes = 0;
-   } else if (tally_source(s, source, &d_text, &nbytes, &rec, &off, &n)) {
+      if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
+      if (use_device(s->device)) return -1;
+   } else if (tally_enter(s, counts, source, NULL, &d_text, &nbytes, &rec, &off, &n)) {
       return -1;
    }
-   if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
-   if (use_device(s->device)) return -1;
    s->th_done = false;                                     /* (the column of the hold before is gone, whatever comes of this one) */
    s->th_n = 0;
    s->th_key_bits = 0;
@@ -108,7 +108,7 @@ static int tally_group_ws_keys(seeqdev_scan *s, size_t n)
    if (tally_ws_keys(s, n) || tally_group_ws_cnt(s)) return -1;
    const size_t nt = (size_t)tally_tiles(n) + 1;
    return ws_grow(&s->ws, &s->cap_tg, n, {{s->tg_g0, n * sizeof(uint64_t)}, {s->tg_g1, n * sizeof(uint64_t)}, {s->tg_sum, 3 * nt * sizeof(uint32_t)},
-                                          {s->tg_stat, nt * SEEQ_TG_STAT * sizeof(uint32_t)}});
+                                          {s->tg_stat, nt * SEEQ_TALLY_STAT * sizeof(uint32_t)}});
 }
 
 /* The two tables of the n member spans rec / off of text[0 .. nbytes) against the held column; the context's tables (tg_pairs: tg_np,
@@ -127,17 +127,12 @@ static int tally_grouped_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *
    a.nt = (uint32_t)tally_tiles(n);
    a.text = (const uint8_t *)d_text; a.nbytes = nbytes;
    a.hold_line = s->th_line; a.hold_key = s->th_key; a.nh = (uint32_t)s->th_n;
-   a.msrc = s->tl_key0; a.mdst = s->tl_key1;
-   a.gsrc = s->tg_g0; a.gdst = s->tg_g1;
-   a.mat = s->tl_mat;
    a.tstat = s->tg_stat;
    a.rsum = s->tg_sum;
    a.cnt = s->d_tgcnt;
-   TallyArgs sa;                                           /* the offsets scan of the digit matrix is the plain tally's, as it is */
-   memset(&sa, 0, sizeof sa);
-   sa.n = n; sa.nt = a.nt;
-   sa.mat = s->tl_mat; sa.nmat = (uint32_t)tally_matrix(n); sa.nb = (uint32_t)tally_chunks(n);
-   sa.bsum = s->tl_sum + 2 * (size_t)a.nt;
+   TallySortArgs sa = tally_sort_args(s, n, s->tg_stat);   /* word 0: the members, in the plain tally's key arrays; word 1: the groups */
+   sa.src[1] = s->tg_g0; sa.dst[1] = s->tg_g1;
+   a.msrc = sa.src[0]; a.gsrc = sa.src[1];
    if ((size_t)n > s->cap_tl || (size_t)n > s->cap_tg || tally_tiles(s->cap_tl) < a.nt || tally_tiles(s->cap_tg) < a.nt || tally_chunks(s->cap_tl) < sa.nb ||
        s->th_n > s->cap_th) {
       snprintf(g_last_error, sizeof g_last_error, "grouped tally: %u spans, arrays for %zu and %zu; %zu held records, arrays for %zu", n, s->cap_tl, s->cap_tg,
@@ -155,20 +150,11 @@ static int tally_grouped_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *
    if ((uint64_t)h.nlong + h.nforeign + h.nthird > n || h.max_len > SEEQ_TALLY_LEN_MAX) return tally_group_fail("pack", h, n, 0);
    const uint64_t npaired = (uint64_t)n - h.nlong - h.nforeign - h.nthird;
    const TallyGroupCnt packed = h;
-   const uint32_t mpasses = tally_passes(h.max_len);
    const uint32_t passes = tally_pair_passes(npaired, h.max_len, s->th_key_bits);
    if (npaired) {
-      for (uint32_t p = 0; p < passes; p++) {
-         a.word = p < mpasses ? 0u : 1u;
-         a.pass = p < mpasses ? p : p - mpasses;
-         hipLaunchKernelGGL(k_tally_pair_hist, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
-         hipLaunchKernelGGL(k_tally_scan_reduce, dim3(sa.nb), dim3(SEEQ_TILE_WG), 0, st, sa);
-         hipLaunchKernelGGL(k_tally_scan_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, sa);
-         hipLaunchKernelGGL(k_tally_scan_apply, dim3(sa.nb), dim3(SEEQ_TILE_WG), 0, st, sa);
-         hipLaunchKernelGGL(k_tally_pair_scatter, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
-         uint64_t *t = a.msrc; a.msrc = a.mdst; a.mdst = t;      /* (the pass's output is the next one's input) */
-         t = a.gsrc; a.gsrc = a.gdst; a.gdst = t;
-      }
+      TallyPass list[SEEQ_TALLY_PASS_MAX];
+      tally_sort_run(st, &sa, 2, list, tally_pass_list(list, tally_passes(h.max_len), tally_group_passes(s->th_key_bits)));
+      a.msrc = sa.src[0]; a.gsrc = sa.src[1];
       hipLaunchKernelGGL(k_tally_pair_rle_reduce, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
       hipLaunchKernelGGL(k_tally_pair_rle_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
       if (counters_fetch(s, s->h_tgcnt, s->d_tgcnt, sizeof(TallyGroupCnt))) return -1;
@@ -179,8 +165,8 @@ static int tally_grouped_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *
       if (ws_grow(&s->ws, &s->cap_tg_pairs, np, {{s->tg_pairs, np * sizeof(seeqdev_tally_pair_t)}})) return -1;
       if (ws_grow(&s->ws, &s->cap_tg_groups, ng, {{s->tg_groups, ng * sizeof(seeqdev_tally_group_t)}})) return -1;
       a.np = h.npairs; a.ng = h.ngroups;
-      a.ppos = (uint32_t *)a.mdst;                         /* (4 bytes per pair head in the 8 bytes per span the last pass left free ...) */
-      a.gpos = (uint32_t *)a.gdst;                         /* (... and 4 + 4 per group head in the group words') */
+      a.ppos = (uint32_t *)sa.dst[0];                      /* (4 bytes per pair head in the 8 bytes per span the last pass left free ...) */
+      a.gpos = (uint32_t *)sa.dst[1];                      /* (... and 4 + 4 per group head in the group words') */
       a.grank = a.gpos + n;
       a.ptab = (uint64_t *)s->tg_pairs; a.gtab = (uint64_t *)s->tg_groups;
       a.cap_ptab = cap_u32(s->cap_tg_pairs); a.cap_gtab = cap_u32(s->cap_tg_groups);
@@ -208,19 +194,11 @@ static int tally_grouped_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *
 
 extern "C" int seeqdevScanTallyGrouped(seeqdev_scan_t *s, int source, const void *d_text, size_t nbytes, seeqdev_tally_grouped_counts_t *counts)
 {
-   seeqerr = 0;
-   if (!s || !counts || (source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS) || (!d_text && nbytes)) { errno = EINVAL; return -1; }
-   if (!s->th_done) {
-      snprintf(g_last_error, sizeof g_last_error, "grouped tally: the context holds no held column (seeqdevScanTallyHold)");
-      errno = EINVAL;
-      return -1;
-   }
    const uint4 *rec;
    const uint64_t *off;
    uint64_t n;
-   if (tally_source(s, source, &d_text, &nbytes, &rec, &off, &n)) return -1;
-   if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
-   if (use_device(s->device)) return -1;
+   const char *missing = s && !s->th_done ? "grouped tally: the context holds no held column (seeqdevScanTallyHold)" : NULL;
+   if (tally_enter(s, counts, source, missing, &d_text, &nbytes, &rec, &off, &n)) return -1;
    s->tg_np = s->tg_ng = 0;                                /* (the tables of the call before are gone, whatever comes of this one) */
    s->tg_done = false;
    s->tc_np = s->tc_ng = 0;                                /* (... and with them what a collapse made of them: seeq_tally_collapse_host.h) */

@@ -28,8 +28,10 @@
  *   the search             a lower bound over the sorted library keys in two levels: a workgroup keeps every stride-th key, 256 samples,
  *                          in LDS (stride = ceil(N / 256)) and a search takes its first eight steps there; what is left is a range of at
  *                          most stride keys of the library itself, searched in at most bitlen(stride) + 1 steps -- a host-known count.
- *                          (A search of bitlen(N) dependent loads from the L2 cost 0.58 ms for 0.9 M misses of 20-mers; the host
- *                          rule's one-level search, tally_lib_lower_bound, is what the driver checks the two levels against.)
+ *                          (A search of bitlen(N) dependent loads from the L2 cost 0.58 ms for 0.9 M misses of 20-mers.)  Every
+ *                          search of the rule side is tally_lower_bound, the one halving loop -- over keys or over a column of a 24-byte
+ *                          table (seeq_tally_collapse.h); tally_lib_lower_bound / _top are calls to it, and the driver checks the two
+ *                          levels against the one search of the whole array.
  *   k_tally_assign_exact   one thread per span, in the tiles of seeq_tiles.h: the search of the span's key, the four searches of a
  *                          thread stepped together (four independent loads in flight).  A found key stores its id AT THE SPAN'S OWN INDEX; a
  *                          nonzero key that is not found is a MISS and stores 0 -- or, when the near pass will follow, the key with
@@ -84,15 +86,26 @@ SEEQ_ST_HD uint32_t tally_lib_probes(uint32_t n) { return tally_lib_bitlen(n) + 
 /* passes of the sort over ids 1 .. n: their bitlen(n) bits in digits of 8; 0 when nothing was assigned */
 SEEQ_ST_HD uint32_t tally_lib_passes(uint64_t nassigned, uint32_t n) { return nassigned ? (tally_lib_bitlen(n) + 7u) / 8u : 0u; }
 
-/* library keys below `key` among lkey[0 .. n), ascending; at most `probes` steps */
-SEEQ_ST_HD uint32_t tally_lib_lower_bound(const uint64_t *lkey, uint32_t n, uint32_t probes, uint64_t key)
+/* One step of a lower-bound search for `key` over the ascending 64-bit keys keys[stride * i], lo <= i < hi (stride in words: 1 for an array
+   of keys, 3 for a column of a 24-byte table): the range is halved; an empty one stays as it is.  The kernels that advance several
+   searches in lock step call this once per search and step. */
+SEEQ_ST_HD void tally_bound_step(const uint64_t *keys, uint32_t stride, uint64_t key, uint32_t *lo, uint32_t *hi)
 {
-   uint32_t lo = 0, hi = n;
-   for (uint32_t it = 0; it < probes && lo < hi; it++) {
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if (lkey[mid] < key) lo = mid + 1u;
-      else hi = mid;
+   if (*lo < *hi) {
+      const uint32_t mid = *lo + (*hi - *lo) / 2u;
+      if (keys[(uint64_t)stride * mid] < key) *lo = mid + 1u;
+      else *hi = mid;
    }
+}
+
+/* THE LOWER BOUND, the one of the rule side: lo + the keys below `key` among keys[stride * i], lo <= i < hi, ascending; at most `probes`
+   steps. */
+SEEQ_ST_HD uint32_t tally_lower_bound(const uint64_t *keys, uint32_t stride, uint32_t lo, uint32_t hi, uint32_t probes, uint64_t key)
+{
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+   for (uint32_t it = 0; it < probes && lo < hi; it++) tally_bound_step(keys, stride, key, &lo, &hi);
    return lo;
 }
 
@@ -119,17 +132,16 @@ SEEQ_ST_HD void tally_lib_top_range(const uint64_t *top, uint32_t n, uint32_t st
    *hi = end < n ? (uint32_t)end : n;
 }
 
-/* the lower bound by both levels: the samples, then at most `probes` = tally_lib_probes(stride) steps over the library */
+/* library keys below `key` among lkey[0 .. n), ascending: by one search of the whole array, and by both levels -- the samples, then at most
+   `probes` = tally_lib_probes(stride) steps over the range they leave (what the kernels do, and what the host driver checks against the
+   first) */
+SEEQ_ST_HD uint32_t tally_lib_lower_bound(const uint64_t *lkey, uint32_t n, uint32_t probes, uint64_t key) { return tally_lower_bound(lkey, 1u, 0u, n, probes, key); }
+
 SEEQ_ST_HD uint32_t tally_lib_lower_bound_top(const uint64_t *top, const uint64_t *lkey, uint32_t n, uint32_t stride, uint32_t probes, uint64_t key)
 {
    uint32_t lo, hi;
    tally_lib_top_range(top, n, stride, key, &lo, &hi);
-   for (uint32_t it = 0; it < probes && lo < hi; it++) {
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if (lkey[mid] < key) lo = mid + 1u;
-      else hi = mid;
-   }
-   return lo;
+   return tally_lower_bound(lkey, 1u, lo, hi, probes, key);
 }
 
 /* the id of `key` in the library, 0: it is no entry */
@@ -230,11 +242,7 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_assign_exact(TallyLibArg
    for (uint32_t it = 0; it < a.probes; it++) {
 #pragma unroll
       for (int k = 0; k < SEEQ_TILE_ITEMS; k++) {
-         if (lo[k] < hi[k]) {
-            const uint32_t mid = lo[k] + (hi[k] - lo[k]) / 2u;      /* (< hi <= nlib) */
-            if (a.lkey[mid] < key[k]) lo[k] = mid + 1u;
-            else hi[k] = mid;
-         }
+         tally_bound_step(a.lkey, 1u, key[k], &lo[k], &hi[k]);      /* (mid < hi <= nlib) */
       }
    }
    uint32_t sum[2] = {0u, 0u};                              /* misses, exact: wave-uniform */
@@ -323,11 +331,7 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_assign_near(TallyLibArgs
       for (uint32_t it = 0; it < a.probes; it++) {
 #pragma unroll
          for (int s = 0; s < 3; s++) {
-            if (lo[s] < hi[s]) {
-               const uint32_t mid = lo[s] + (hi[s] - lo[s]) / 2u;      /* (< hi <= nlib) */
-               if (a.lkey[mid] < nb[s]) lo[s] = mid + 1u;
-               else hi[s] = mid;
-            }
+            tally_bound_step(a.lkey, 1u, nb[s], &lo[s], &hi[s]);      /* (mid < hi <= nlib) */
          }
       }
       uint32_t nfound = 0, idsum = 0;                       /* (one neighbour found: the sum of the ids found is its id) */

@@ -1,8 +1,8 @@
 /*
  * seeq_tally_library_host.h -- the host driver of the tally against a known library (rule and kernels: seeq_tally_library.h): the set
  * call's validation, sort and upload, the assignment of a key array in place -- the exact pass, and under max_mismatch 1 the compaction of
- * the misses and the near pass -- between the plain tally's pack (or the grouped tally's hold) and what follows it, and the
- * seeqdevScanSetLibrary / seeqdevScanTallyLibrary / seeqdevScanTallyHoldLibrary entries.  Included by seeq_device.hip behind
+ * the misses and the near pass -- as the step of tally_run (seeq_tally_host.h) between its pack and its sort, or behind the grouped
+ * tally's hold, and the seeqdevScanSetLibrary / seeqdevScanTallyLibrary / seeqdevScanTallyHoldLibrary entries.  Included by seeq_device.hip behind
  * seeq_tally_group_host.h.
  */
 #ifndef SEEQ_TALLY_LIBRARY_HOST_H_
@@ -110,112 +110,62 @@ static void tally_library_counts(seeqdev_tally_library_counts_t *counts, const T
    counts->nassigned = (uint64_t)l.nexact + l.ncorrected;
 }
 
-/* The table of the n spans rec / off of text[0 .. nbytes) against the library; the context's table (tl_tab, tl_n) is the result: tally_run
-   with the assignment between its pack and its sort, and the sort's passes from the library's size.  Waits. */
-static int tally_library_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uint32_t n, const void *d_text, size_t nbytes,
-                             seeqdev_tally_library_counts_t *counts)
+/* THE LIBRARY AS tally_run's STEP between its pack and its sort: the assignment of the key array in place, the sort's passes from the
+   library's size, and the library's numbers beside the tally's in the text of an inconsistency. */
+struct TallyLibStep : TallyStep {
+   TallyLibCnt l;                     /* the assignment's five counts */
+   uint64_t    nkeyed;                /* the spans with a key it saw */
+};
+
+static int tally_library_step_fail(const TallyStep *step, const char *what, const TallyCnt &h, uint32_t n, uint64_t nassigned)
 {
-   const hipStream_t st = s->stream;
-   memset(counts, 0, sizeof *counts);
-   counts->nspans = n;
-   counts->key_bits = tally_lib_bitlen(s->lb_n);
-   if (!n) return 0;                                       /* no spans: nothing is launched */
-   if (tally_ws_keys(s, n)) return -1;
-   TallyArgs a;
-   memset(&a, 0, sizeof a);
-   a.rec = rec; a.off = off; a.n = n;
-   a.nt = (uint32_t)tally_tiles(n);
-   a.text = (const uint8_t *)d_text; a.nbytes = nbytes;
-   a.src = s->tl_key0; a.dst = s->tl_key1;
-   a.mat = s->tl_mat; a.nmat = (uint32_t)tally_matrix(n); a.nb = (uint32_t)tally_chunks(n);
-   a.rsum = s->tl_sum; a.bsum = s->tl_sum + 2 * (size_t)a.nt;
-   a.tstat = s->tl_stat;
-   a.cnt = s->d_tlcnt;
-   if ((size_t)n > s->cap_tl || tally_tiles(s->cap_tl) < a.nt || tally_chunks(s->cap_tl) < a.nb) {
-      snprintf(g_last_error, sizeof g_last_error, "library tally: %u spans, arrays for %zu", n, s->cap_tl);
-      errno = EIO;
-      return -1;
-   }
-   if (s->tm_tl.begin(s->prof, st)) return -1;
-   HIP_TRY(hipMemsetAsync(s->d_tlcnt, 0, sizeof(TallyCnt), st), EIO);
-   hipLaunchKernelGGL(k_tally_pack, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
-   hipLaunchKernelGGL(k_tally_pack_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
-   if (counters_fetch(s, s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt))) return -1;
-   TallyCnt h = *s->h_tlcnt;
-   if (h.bad) {
-      snprintf(g_last_error, sizeof g_last_error, "library tally: a span lies outside the %zu bytes of text it was given", nbytes);
-      errno = EIO;
-      return -1;
-   }
-   TallyLibCnt l = {};
-   if ((uint64_t)h.nlong + h.nforeign > n || h.max_len > SEEQ_TALLY_LEN_MAX) return tally_library_fail("pack", l, h, n, 0, 0, s->lb_n);
-   const uint64_t nkeyed = (uint64_t)n - h.nlong - h.nforeign;
-   const TallyCnt packed = h;
-   if (nkeyed && tally_library_assign(s, a.src, (uint32_t *)a.dst, n, nkeyed, &l)) return -1;      /* (4 bytes per miss in the 8 per span the sort has not touched yet) */
-   const uint64_t nassigned = (uint64_t)l.nexact + l.ncorrected;
-   if ((uint64_t)l.nexact + l.ncorrected + l.nambiguous + l.nunknown + packed.nlong + packed.nforeign != n)
-      return tally_library_fail("kinds", l, h, n, nkeyed, nassigned, s->lb_n);
-   const uint32_t passes = tally_lib_passes(nassigned, (uint32_t)s->lb_n);
-   if (nassigned) {
-      for (uint32_t p = 0; p < passes; p++) {
-         a.pass = p;
-         hipLaunchKernelGGL(k_tally_hist, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
-         hipLaunchKernelGGL(k_tally_scan_reduce, dim3(a.nb), dim3(SEEQ_TILE_WG), 0, st, a);
-         hipLaunchKernelGGL(k_tally_scan_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
-         hipLaunchKernelGGL(k_tally_scan_apply, dim3(a.nb), dim3(SEEQ_TILE_WG), 0, st, a);
-         hipLaunchKernelGGL(k_tally_scatter, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
-         uint64_t *t = a.src; a.src = a.dst; a.dst = t;     /* (the pass's output is the next one's input) */
-      }
-      hipLaunchKernelGGL(k_tally_rle_reduce, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
-      hipLaunchKernelGGL(k_tally_rle_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
-      if (counters_fetch(s, s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt))) return -1;
-      h = *s->h_tlcnt;
-      if (h.bad || h.nonzero != nassigned || h.ndistinct == 0 || h.ndistinct > nassigned || h.ndistinct > s->lb_n)
-         return tally_library_fail("sort", l, h, n, nkeyed, nassigned, s->lb_n);
-      const size_t nd = h.ndistinct;
-      if (ws_grow(&s->ws, &s->cap_tl_tab, nd, {{s->tl_tab, nd * sizeof(seeqdev_tally_t)}})) return -1;
-      a.nd = h.ndistinct;
-      a.pos = (uint32_t *)a.dst;                           /* (4 bytes per head in the 8 bytes per span the last pass left free) */
-      a.tab = (uint4 *)s->tl_tab;
-      a.cap_tab = cap_u32(s->cap_tl_tab);
-      hipLaunchKernelGGL(k_tally_rle_apply, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
-      hipLaunchKernelGGL(k_tally_table, dim3((unsigned)((nd + SEEQ_TILE_WG - 1) / SEEQ_TILE_WG)), dim3(SEEQ_TILE_WG), 0, st, a);
-      if (counters_copy(s, s->h_tlcnt, s->d_tlcnt, sizeof(TallyCnt))) return -1;
-   }
-   if (s->tm_tl.end(s->prof, st)) return -1;
-   HIP_TRY(hipStreamSynchronize(st), EIO);
-   s->tm_tl.read(s->prof);
-   if (nassigned) {
-      h = *s->h_tlcnt;
-      /* the counts of the table telescope to n - the first head's index: the ids that are 0 lie before it */
-      if (h.bad || (uint64_t)n - h.first != nassigned) return tally_library_fail("table", l, h, n, nkeyed, nassigned, s->lb_n);
-      s->tl_n = h.ndistinct;
-      counts->ndistinct = h.ndistinct;
-   }
-   tally_library_counts(counts, l);
-   counts->nlong = packed.nlong; counts->nforeign = packed.nforeign;
-   counts->passes = passes;
+   const TallyLibStep *ls = (const TallyLibStep *)step;
+   return tally_library_fail(what, ls->l, h, n, ls->nkeyed, nassigned, ls->max_distinct);
+}
+
+static int tally_library_step(seeqdev_scan *s, TallyStep *step, uint64_t *key, uint32_t *scratch, uint32_t n, uint64_t nkeyed, const TallyCnt &packed, uint64_t *nleft,
+                              uint32_t *passes)
+{
+   TallyLibStep *ls = (TallyLibStep *)step;
+   ls->nkeyed = nkeyed;
+   if (nkeyed && tally_library_assign(s, key, scratch, n, nkeyed, &ls->l)) return -1;      /* (4 bytes per miss in the 8 per span the sort has not touched yet) */
+   const TallyLibCnt &l = ls->l;
+   *nleft = (uint64_t)l.nexact + l.ncorrected;
+   if ((uint64_t)l.nexact + l.ncorrected + l.nambiguous + l.nunknown + packed.nlong + packed.nforeign != n) return tally_library_step_fail(step, "kinds", packed, n, *nleft);
+   *passes = tally_lib_passes(*nleft, (uint32_t)s->lb_n);
    return 0;
 }
 
-static int tally_library_none(void)
+/* The table of the n spans rec / off of text[0 .. nbytes) against the library; the context's table (tl_tab, tl_n) is the result: tally_run
+   with the step above, and its counts beside the assignment's.  Waits. */
+static int tally_library_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uint32_t n, const void *d_text, size_t nbytes,
+                             seeqdev_tally_library_counts_t *counts)
 {
-   snprintf(g_last_error, sizeof g_last_error, "library tally: the context holds no library (seeqdevScanSetLibrary)");
-   errno = EINVAL;
-   return -1;
+   memset(counts, 0, sizeof *counts);
+   counts->nspans = n;
+   counts->key_bits = tally_lib_bitlen(s->lb_n);
+   TallyLibStep step = {};
+   step.who = "library tally"; step.max_distinct = s->lb_n;
+   step.rewrite = tally_library_step; step.fail = tally_library_step_fail;
+   seeqdev_tally_counts_t t;
+   if (tally_run(s, rec, off, n, d_text, nbytes, &t, &step)) return -1;
+   tally_library_counts(counts, step.l);
+   counts->nlong = t.nlong; counts->nforeign = t.nforeign;
+   counts->ndistinct = t.ndistinct; counts->passes = t.passes;
+   return 0;
+}
+
+static const char *tally_library_missing(const seeqdev_scan *s)
+{
+   return s && !s->lb_n ? "library tally: the context holds no library (seeqdevScanSetLibrary)" : NULL;
 }
 
 extern "C" int seeqdevScanTallyLibrary(seeqdev_scan_t *s, int source, const void *d_text, size_t nbytes, seeqdev_tally_library_counts_t *counts)
 {
-   seeqerr = 0;
-   if (!s || !counts || (source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS) || (!d_text && nbytes)) { errno = EINVAL; return -1; }
-   if (!s->lb_n) return tally_library_none();
    const uint4 *rec;
    const uint64_t *off;
    uint64_t n;
-   if (tally_source(s, source, &d_text, &nbytes, &rec, &off, &n)) return -1;
-   if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
-   if (use_device(s->device)) return -1;
+   if (tally_enter(s, counts, source, tally_library_missing(s), &d_text, &nbytes, &rec, &off, &n)) return -1;
    s->tl_n = 0;                                            /* (the table of the tally before, of either kind, is gone, whatever comes of this one) */
    s->tm_tl.ms = 0.f;
    return tally_library_run(s, rec, off, (uint32_t)n, d_text, nbytes, counts);
@@ -223,15 +173,10 @@ extern "C" int seeqdevScanTallyLibrary(seeqdev_scan_t *s, int source, const void
 
 extern "C" int seeqdevScanTallyHoldLibrary(seeqdev_scan_t *s, int source, const void *d_text, size_t nbytes, seeqdev_tally_library_counts_t *counts)
 {
-   seeqerr = 0;
-   if (!s || !counts || (source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS) || (!d_text && nbytes)) { errno = EINVAL; return -1; }
-   if (!s->lb_n) return tally_library_none();
    const uint4 *rec;
    const uint64_t *off;
    uint64_t n;
-   if (tally_source(s, source, &d_text, &nbytes, &rec, &off, &n)) return -1;
-   if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
-   if (use_device(s->device)) return -1;
+   if (tally_enter(s, counts, source, tally_library_missing(s), &d_text, &nbytes, &rec, &off, &n)) return -1;
    s->th_done = false;                                     /* (the column of the hold before is gone, whatever comes of this one) */
    s->th_n = 0;
    s->th_key_bits = 0;
