@@ -385,6 +385,7 @@ int seeqdevScanLastInsertsMs(const seeqdev_scan_t * scan, float * join_ms);
  *                        SEEQDEV_TALLY_HITS: bytes [start, end) of the records seeqdevScanCopyRecords serves now -- those of a plain scan
  *                        fetched with SEEQDEV_WANT_RECORDS, or of a both-strands call.  A minus-strand hit is tallied as the bytes of
  *                        the text, NOT reverse-complemented.
+ *                        SEEQDEV_TALLY_GATED: the records the context's last quality gate passed (THE BASE-QUALITY GATE below).
  *   key                  of a span of L <= SEEQDEV_TALLY_MAX_LEN bases, every byte one of ACGTUacgtu:
  *                        (1 << 2L) | sum of code(b_i) << 2(L - 1 - i), code = (ASCII >> 1) & 3 as in the packed batches below
  *                        (A 0, C 1, T/U 2, G 3).  The leading 1 carries the length: the empty span has key 1; bit 63 is never set;
@@ -619,6 +620,57 @@ typedef struct {
 int seeqdevScanSetLibrary(seeqdev_scan_t * scan, const uint64_t * keys, size_t n, int max_mismatch);
 int seeqdevScanTallyLibrary    (seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_library_counts_t * counts);
 int seeqdevScanTallyHoldLibrary(seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_library_counts_t * counts);
+
+/* THE BASE-QUALITY GATE -- every FASTQ counting pipeline puts a bar on the base qualities of what it counts ("drop the UMI if any base is
+ * below Q", "at most k bases below Q in the barcode"): an uncertain base is what makes the spurious distinct keys, the corrected library
+ * hits and the absorbed UMI pairs.  seeqdevScanQualityGate reads, ON THE DEVICE, the quality bytes under every span of a record array --
+ * the fourth line of the span's FASTQ record -- and keeps the records whose span passes in arrays of its own, which
+ * SEEQDEV_TALLY_GATED names as the source of seeqdevScanTally, seeqdevScanTallyLibrary, seeqdevScanTallyHold,
+ * seeqdevScanTallyHoldLibrary and seeqdevScanTallyGrouped: they run unchanged over the gated records.
+ *   source               SEEQDEV_TALLY_INSERTS or SEEQDEV_TALLY_HITS, with the preconditions and the NULL-text rule of seeqdevScanTally;
+ *                        anything else (SEEQDEV_TALLY_GATED and SEEQDEV_TALLY_DEMUX included): EINVAL.
+ *   the rule             positional, like SEEQDEV_FASTQ: nothing looks for '@' or '+'.  A span is bytes [start, end) of the line at its
+ *                        offset `off`.  Its kind, decided in this order:
+ *                          bad     end < start, or it reaches beyond nbytes: no byte is loaded, the call fails with EIO (the context
+ *                                  stays usable);
+ *                          long    more than SEEQDEV_TALLY_MAX_LEN bytes: nothing is read, it is not passed (no tally would count it);
+ *                          far / misfit  with p = off + end, e1 the first '\n' at or behind p and e2 the first one behind e1, both
+ *                                  searched in [p, min(nbytes, p + reach)) only: without an e2 there the span is FAR when p + reach <
+ *                                  nbytes (the text goes on beyond the reach), MISFIT otherwise (the text ends first);
+ *                          misfit  with q0 = e2 + 1 and seqlen = e1 - off: unless q0 + seqlen <= nbytes, and unless q0 + seqlen ==
+ *                                  nbytes or text[q0 + seqlen] == '\n' (the line two below ends where a quality line of the sequence
+ *                                  line's length ends: one byte probe that catches truncated and misaligned records, no validator);
+ *                          low     more than max_low of the quality bytes text[q0 + start .. q0 + end) are below base + min_qual
+ *                                  (unsigned bytes; '\n' and '\r' like any other);
+ *                          pass    otherwise; an empty span that fits passes.
+ *                        Nothing outside [0, nbytes) is read.
+ *   counts               nspans == npassed + nlow + nlong + nfar + nmisfit; low_bases: the low bytes seen in passed and low spans.
+ * EINVAL, before any device call: NULL scan / counts, an unknown source, NULL text with bytes, base + min_qual > 255, reach outside
+ * 1 .. 65536, and seeqdevScanTally's cases for the source.  E2BIG: more than 2^32 - 1 spans.  EIO: a bad span, or an internal
+ * inconsistency (the kinds must sum to nspans, the compaction must have placed npassed records).
+ * Synchronous.  The call reads the source arrays and writes only its own: the record arrays, what there is to fetch, the inserts result,
+ * the held column, every tally table and the library are afterwards what they were.  The gated arrays -- seeqdevScanGatedDevice /
+ * seeqdevScanCopyGated (the 16-byte records unchanged: line, dist with SEEQDEV_HIT_MINUS, both distances of an insert record) /
+ * seeqdevScanCopyGatedOffsets, and seeqdevScanCopyGateKinds (one kind per SOURCE record) -- are COPIES: valid across later scans and
+ * inserts calls, until the context's next gate or seeqdevScanFree.  A gate that passed nothing is a result (a tally over it launches
+ * nothing); without a completed gate SEEQDEV_TALLY_GATED is EINVAL.  A tally over SEEQDEV_TALLY_GATED is given the text the gated records
+ * were found in; NULL is legal only when the gate's own source was the inserts: the staged text, as there.
+ * Device memory of its own: 1 byte per source record, 28 bytes per tile of 1 024, 24 bytes per passed record.  (The reference reads no
+ * quality line: an addition of this boundary.) */
+#define SEEQDEV_TALLY_GATED 4   /* the spans the context's last quality gate passed */
+#define SEEQDEV_QGATE_PASS   0  /* the kinds seeqdevScanCopyGateKinds serves */
+#define SEEQDEV_QGATE_LOW    1
+#define SEEQDEV_QGATE_LONG   2
+#define SEEQDEV_QGATE_FAR    3
+#define SEEQDEV_QGATE_MISFIT 4
+typedef struct { uint64_t nspans, npassed, nlow, nlong, nfar, nmisfit, low_bases; } seeqdev_qgate_counts_t;   /* 56 bytes */
+int seeqdevScanQualityGate(seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes,
+                           uint32_t min_qual, uint32_t base, uint32_t max_low, uint32_t reach, seeqdev_qgate_counts_t * counts);
+const seeqdev_hit_t * seeqdevScanGatedDevice(const seeqdev_scan_t * scan);
+int seeqdevScanCopyGated       (seeqdev_scan_t * scan, void * host_out /* 16-byte records */, size_t first, size_t n);
+int seeqdevScanCopyGatedOffsets(seeqdev_scan_t * scan, uint64_t * host_out, size_t first, size_t n);
+int seeqdevScanCopyGateKinds   (seeqdev_scan_t * scan, uint8_t * host_out, size_t first, size_t n);   /* one kind per SOURCE record */
+int seeqdevScanLastQualityGateMs(const seeqdev_scan_t * scan, float * ms);
 
 /* PACKED READ BATCHES -- 2 bits per base instead of a byte: a quarter of the HBM (and PCIe) traffic of the ASCII scan for
  * read sets that are kept packed anyway (BAM, .2bit, a sequencer's own format).  Layout, all device pointers:

@@ -126,6 +126,15 @@ class seeqdev_tally_library_counts_t(C.Structure):
                 ("passes", C.c_uint32)]
 
 
+SEEQDEV_TALLY_GATED = 4             # the spans the context's last quality gate passed
+SEEQDEV_QGATE_PASS, SEEQDEV_QGATE_LOW, SEEQDEV_QGATE_LONG, SEEQDEV_QGATE_FAR, SEEQDEV_QGATE_MISFIT = 0, 1, 2, 3, 4
+
+
+class seeqdev_qgate_counts_t(C.Structure):
+    _fields_ = [("nspans", C.c_uint64), ("npassed", C.c_uint64), ("nlow", C.c_uint64), ("nlong", C.c_uint64), ("nfar", C.c_uint64),
+                ("nmisfit", C.c_uint64), ("low_bases", C.c_uint64)]
+
+
 # Every symbol the three public headers declare (tests check the .so exports all of them).
 EXPORTS = [
     # libseeq.h
@@ -151,6 +160,8 @@ EXPORTS = [
     "seeqdevScanTallyCollapse", "seeqdevScanTallyParentsDevice", "seeqdevScanTallyCollapseDevice", "seeqdevScanCopyTallyParents",
     "seeqdevScanCopyTallyCollapse", "seeqdevScanLastTallyCollapseMs",
     "seeqdevScanSetLibrary", "seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary",
+    "seeqdevScanQualityGate", "seeqdevScanGatedDevice", "seeqdevScanCopyGated", "seeqdevScanCopyGatedOffsets", "seeqdevScanCopyGateKinds",
+    "seeqdevScanLastQualityGateMs",
     "seeqdevScanLastRuns", "seeqdevScanFallback", "seeqdevScanLastPlan",
 ]
 
@@ -352,6 +363,15 @@ def lib():
     for name in ("seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary"):
         getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(seeqdev_tally_library_counts_t)]
         getattr(L, name).restype = C.c_int
+    L.seeqdevScanQualityGate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(seeqdev_qgate_counts_t)]
+    L.seeqdevScanQualityGate.restype = C.c_int
+    L.seeqdevScanGatedDevice.argtypes = [C.c_void_p]
+    L.seeqdevScanGatedDevice.restype = C.c_void_p
+    for name in ("seeqdevScanCopyGated", "seeqdevScanCopyGatedOffsets", "seeqdevScanCopyGateKinds"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        getattr(L, name).restype = C.c_int
+    L.seeqdevScanLastQualityGateMs.argtypes = [C.c_void_p, P(C.c_float)]
+    L.seeqdevScanLastQualityGateMs.restype = C.c_int
     L.seeqdevScanPacked.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(seeqdev_packed_t), C.c_int, C.c_int]
     L.seeqdevScanPacked.restype = C.c_int
     L.seeqdevPackReads.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]

@@ -114,6 +114,7 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_tally_group.h"
 #include "seeq_tally_library.h"
 #include "seeq_tally_collapse.h"
+#include "seeq_qgate.h"
 static_assert(sizeof(seeqdev_tally_pair_t) == 24 && sizeof(seeqdev_tally_group_t) == 24, "pair and group entries are written as three 64-bit words");
 static_assert(sizeof(seeqdev_tally_collapse_t) == sizeof(uint4) && SEEQ_COLLAPSE_DIRECTIONAL == SEEQDEV_COLLAPSE_DIRECTIONAL && SEEQ_COLLAPSE_ANY == SEEQDEV_COLLAPSE_ANY,
               "collapse rows are written as uint4");
@@ -588,6 +589,15 @@ struct seeqdev_scan {
    CollapseCnt *d_tccnt, *h_tccnt;                        /* h_ pinned */
    size_t    tc_np, tc_ng;                                /* entries of the last collapse's two arrays */
    EventPair tm_tc;                                       /* profiling: around the collapse's launches and its counters copy */
+   /* seeqdevScanQualityGate (seeq_qgate.h): allocated by the first gate.  It reads a source's record arrays and writes these; the kinds
+      (qg_kind: qg_nsrc source records) and the passed records (qg_rec, qg_off: qg_n) are copies, valid until the next gate */
+   uint8_t  *qg_kind; uint32_t *qg_bsum; size_t cap_qg;   /* per source record: its kind; per tile: the seven numbers */
+   uint4    *qg_rec; uint64_t *qg_off; size_t cap_qg_out; /* the passed records and their line offsets */
+   QGateCnt *d_qgcnt, *h_qgcnt;                           /* h_ pinned */
+   size_t    qg_n, qg_nsrc;                               /* passed records; source records of the last gate */
+   bool      qg_done;                                     /* a gate has completed: qg_n records (none included) are a result */
+   bool      qg_from_inserts;                             /* ... and its source was the inserts: a NULL text is the staged one */
+   EventPair tm_qg;                                       /* profiling: around the gate's launches and counter copies */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -710,7 +720,7 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
 {
    if (!s) return;
    (void)use_device(s->device);
-   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl, &s->tm_tg, &s->tm_tc})
+   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl, &s->tm_tg, &s->tm_tc, &s->tm_qg})
       if (t->made) { (void)hipEventDestroy(t->ev[0]); (void)hipEventDestroy(t->ev[1]); }
    (void)hipStreamSynchronize(s->stream);
    ws_free_all(&s->ws);
@@ -1883,6 +1893,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 #include "seeq_tally_group_host.h"
 #include "seeq_tally_library_host.h"
 #include "seeq_tally_collapse_host.h"
+#include "seeq_qgate_host.h"
 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {

@@ -430,7 +430,7 @@ class Scanner:
         staged.  -> dict: nspans, ntallied, nlong, nforeign, ndistinct, max_len, passes; copy adds keys and counts, uint64 arrays in
         ascending key order (by length, then A < C < T < G): tally_key / tally_decode / tally_lookup.  copy=False leaves the table on
         the device (tally_device_ptr / tally_table)."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS}.get(source, source)
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
         cnt = _capi.seeqdev_tally_counts_t()
         _check(self._lib.seeqdevScanTally(self._h, src, C.c_void_p(t.data_ptr()) if t is not None else None, t.numel() if t is not None else 0, C.byref(cnt)))
         res = dict(nspans=int(cnt.nspans), ntallied=int(cnt.ntallied), nlong=int(cnt.nlong), nforeign=int(cnt.nforeign), ndistinct=int(cnt.ndistinct),
@@ -468,7 +468,8 @@ class Scanner:
         winning pattern + 1 of the last demultiplex ("demux"; t is not needed; an ambiguous line is held without a key).  t: as in
         tally().  -> dict: nspans, nheld, nlong, nforeign, nambiguous, max_len, key_bits.  The column survives scans, inserts calls,
         demultiplexes and plain tallies; the next tally_hold replaces it."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX}.get(source, source)
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX,
+               "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
         cnt = _capi.seeqdev_tally_hold_counts_t()
         _check(self._lib.seeqdevScanTallyHold(self._h, src, *self._text_args(t), C.byref(cnt)))
         return dict(nspans=int(cnt.nspans), nheld=int(cnt.nheld), nlong=int(cnt.nlong), nforeign=int(cnt.nforeign), nambiguous=int(cnt.nambiguous),
@@ -482,7 +483,7 @@ class Scanner:
         matrix in row order) and groups (TALLY_GROUP_DTYPE: per group its reads, the rank of its first pair and its distinct members:
         tally_members).  copy=False leaves both on the device (tally_pairs_device_ptr / tally_pairs_table, tally_groups_device_ptr /
         tally_groups_table)."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS}.get(source, source)
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
         cnt = _capi.seeqdev_tally_grouped_counts_t()
         _check(self._lib.seeqdevScanTallyGrouped(self._h, src, *self._text_args(t), C.byref(cnt)))
         res = dict(nspans=int(cnt.nspans), npaired=int(cnt.npaired), nlong=int(cnt.nlong), nforeign=int(cnt.nforeign), nungrouped=int(cnt.nungrouped),
@@ -588,7 +589,7 @@ class Scanner:
         nambiguous, nunknown, nlong, nforeign, ndistinct, key_bits, passes; copy adds ids and counts, uint64 arrays in ascending id
         order, entries without a read absent (library_counts makes the dense vector).  The table is the Scanner's tally table
         (tally_device_ptr / tally_table, `key` = id), replaced by the next tally of either kind."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS}.get(source, source)
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
         cnt = _capi.seeqdev_tally_library_counts_t()
         _check(self._lib.seeqdevScanTallyLibrary(self._h, src, *self._text_args(t), C.byref(cnt)))
         res = self._library_counts(cnt)
@@ -602,10 +603,59 @@ class Scanner:
         """tally_hold ("inserts" or "hits") with the held keys assigned to the library: the group of a line is its entry's id, or none.
         A following tally_grouped has one group per library entry seen, erroneous copies folded into their entry.  -> the dict of
         tally_library (ndistinct and passes 0)."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX}.get(source, source)
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX,
+               "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
         cnt = _capi.seeqdev_tally_library_counts_t()
         _check(self._lib.seeqdevScanTallyHoldLibrary(self._h, src, *self._text_args(t), C.byref(cnt)))
         return self._library_counts(cnt)
+
+    # ---- the base-quality gate in front of the tallies (include/seeq_amd.h: seeqdevScanQualityGate) ----
+    def quality_gate(self, t=None, source="inserts", min_qual=20, base=33, max_low=0, reach=1024, copy=True):
+        """Keep the spans of `source` ("inserts" or "hits", t as in tally()) whose FASTQ quality bytes are good enough: a span passes when
+        at most max_low of the quality bytes under it -- in the line two below its own, found within `reach` bytes behind the span --
+        are below base + min_qual.  Decided and compacted on the device; the tallies then take source="gated".  -> dict: nspans,
+        npassed, nlow, nlong, nfar, nmisfit, low_bases; copy adds records ([npassed, 4] uint32: the source's 16-byte records unchanged,
+        in order), offsets (uint64) and kinds (uint8 per SOURCE record: GATE_PASS, GATE_LOW, GATE_LONG, GATE_FAR, GATE_MISFIT).  The
+        gated arrays are copies: they survive later scans and inserts calls, until the next quality_gate."""
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS}.get(source, source)
+        cnt = _capi.seeqdev_qgate_counts_t()
+        _check(self._lib.seeqdevScanQualityGate(self._h, src, *self._text_args(t), min_qual, base, max_low, reach, C.byref(cnt)))
+        res = {name: int(getattr(cnt, name)) for name, _ in _capi.seeqdev_qgate_counts_t._fields_}
+        if copy:
+            res["records"] = self.gated_records(res["npassed"])
+            res["offsets"] = self.gated_offsets(res["npassed"])
+            res["kinds"] = self.gate_kinds(res["nspans"])
+        return res
+
+    def gated_records(self, n, first=0):
+        """Copy records [first, first + n) the last quality gate passed to the host -> ndarray [n, 4] u32: the words of the source's
+        records (hits: line, start, end, dist with its strand bit; inserts: view as INSERT_DTYPE)."""
+        out = np.zeros((n, 4), dtype=np.uint32)
+        _check(self._lib.seeqdevScanCopyGated(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def gated_offsets(self, n, first=0):
+        """Per gated record: byte offset of its line in the scanned buffer -> ndarray [n] u64."""
+        out = np.zeros(n, dtype=np.uint64)
+        _check(self._lib.seeqdevScanCopyGatedOffsets(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def gate_kinds(self, n, first=0):
+        """Per record of the last quality gate's SOURCE: what its span was -> ndarray [n] u8."""
+        out = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.seeqdevScanCopyGateKinds(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def gated_device_ptr(self):
+        """Device address of the records the last quality gate passed (16 bytes each; valid until this Scanner's next quality_gate);
+        None when it passed none."""
+        return self._lib.seeqdevScanGatedDevice(self._h)
+
+    def last_quality_gate_ms(self):
+        """Device time of the last quality gate (its launches and counter copies; profiling on), 0 when not measured."""
+        ms = C.c_float(0)
+        _check(self._lib.seeqdevScanLastQualityGateMs(self._h, C.byref(ms)))
+        return float(ms.value)
 
     # ---- several patterns, one text (include/seeq_amd.h: seeqdevScanRunMulti / seeqdevScanHostMulti) ----
     def _multi(self, patterns, call, want, copy=True):
@@ -694,6 +744,9 @@ INSERT_DTYPE = np.dtype([("line", "<u4"), ("start", "<u4"), ("end", "<u4"), ("ld
 
 # One entry of seeqdevScanTally's table (seeq_amd.h: seeqdev_tally_t, 16 bytes).
 TALLY_DTYPE = np.dtype([("key", "<u8"), ("count", "<u8")])
+# what Scanner.quality_gate's `kinds` hold, per source record
+GATE_PASS, GATE_LOW, GATE_LONG, GATE_FAR, GATE_MISFIT = (_capi.SEEQDEV_QGATE_PASS, _capi.SEEQDEV_QGATE_LOW, _capi.SEEQDEV_QGATE_LONG,
+                                                         _capi.SEEQDEV_QGATE_FAR, _capi.SEEQDEV_QGATE_MISFIT)
 
 
 def tally_key(seq):
