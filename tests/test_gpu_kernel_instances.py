@@ -16,12 +16,15 @@ A row's text (kernel_instances.build_text) is made from the row's pattern:
 Every row is asserted not to be vacuous (kernel_instances.vacuity), to have run the instance it names in ONE run, on the plan the host planner
 predicts, and to give the oracle's counts, records and line offsets bit for bit -- then once more on a fresh context that scans in 64 KiB
 segments: the same instance again, in one run, or -- where the exact pass walks k_pair's candidate windows -- in a second one that the seam
-flag alone asked for and that differs in nothing but those windows.  Two more tests pin what Scanner.last_plan() says after a fall-back
+flag alone asked for and that differs in nothing but those windows.  A second test per row gives the same text as a window of a larger tensor,
+at an odd and at a 16-aligned lead, between guards whose bytes would change the answer if a kernel used them (tests/text_window.py), and
+once more in segments.  Two more tests pin what Scanner.last_plan() says after a fall-back
 re-run and after a packed run."""
 import numpy as np
 import pytest
 
 import kernel_instances as K
+import text_window as W
 
 pytestmark = pytest.mark.gpu
 
@@ -165,6 +168,98 @@ def test_instance_against_the_oracle(gpu, capi, shared, row, monkeypatch):
         _compare("64 KiB segments, no final newline", sc, res, exp, exp_all, row.want, offsets)
     finally:
         sc.close()
+
+
+class _Window:
+    """a row's hostile window in the shape Shared.expected takes (buf)"""
+
+    def __init__(self, buf):
+        self.buf = buf
+
+
+_WINDOWS = {}       # (id of the row's text, pattern, tau, non-DNA mode, FASTA, closed) -> (_Window, before, after): rows that share a text share its window
+SEEN = {}           # scan kernel -> the residues modulo 4096 of the leads it ran at
+
+
+def _hostile_window(shared, row, i, plan):
+    nd = row.options & 0x0C
+    key = (id(row.text(plan)), row.pattern, row.tau, nd, row.fasta, bool(i % 2))
+    if key not in _WINDOWS:
+        if len(_WINDOWS) > 8:
+            _WINDOWS.clear()
+
+        def hits(buf):
+            e = shared.oracle.buffer_scan(row.pattern, row.tau, buf, K.SQ_ALL | nd, fasta=row.fasta)
+            return W.abs_hits(e["records"], W.line_offsets(buf, row.fasta))
+        window, before, after, _ = W.row_case(row, i, hits, plan)
+        _WINDOWS[key] = (row.text(plan), _Window(window), before, after)
+    return _WINDOWS[key][1:]
+
+
+@pytest.mark.parametrize("i", range(len(ROWS)), ids=[r.key.replace(" | ", "|") for r in ROWS])
+def test_instance_on_a_hostile_window(gpu, capi, shared, i, monkeypatch):
+    """Where the text lies and what surrounds it changes nothing (tests/text_window.py; tests/test_text_window_host.py shows on the CPU that
+    every placement here is live: a kernel that used a byte outside the window would answer otherwise).  The row's text behind a first line
+    that is the second half of an occurrence whose first half ends the guard (FASTA rows: the guard ends in `>`), and in front of a last
+    line that is the first half of one (even rows; no final newline) or of a guard that begins with a line holding one (odd rows) --
+    at an odd lead in a larger tensor and at a lead that is 16-aligned and not 128-aligned: the instance the row names, in one run, on the
+    plan the host planner predicts (no planner input depends on the address), the oracle's counts, records and line offsets of the window's
+    bytes alone.  Then the odd placement once more on a fresh context in 64 KiB segments."""
+    import torch
+    from seeq_amd import device as dev
+    row = ROWS[i]
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in row.knobs.items():
+        monkeypatch.setenv(k, v)
+    plan = row.plan()
+    assert K.instance_key(plan, row.options, row.want) == row.key
+    text, before, after = _hostile_window(shared, row, i, plan)
+    assert len(text.buf) < (1 << 20) + W.TILE_BYTES + 256
+    mode = (row.options & 3) if row.want == dev.WANT_RECORDS else K.SQ_ALL
+    exp_all = shared.expected(row, text, K.SQ_ALL)
+    exp = shared.expected(row, text, mode)
+    offsets = _offsets(text.buf if text.buf.endswith(b"\n") else text.buf + b"\n", row.fasta)
+    pat = shared.pattern(row.pattern, row.tau)
+    odd = None
+    for lead in (W.odd_lead(i), W.aligned_lead(i)):
+        big, lo, hi = W.place(text.buf, lead, before, after)
+        t = torch.frombuffer(bytearray(big), dtype=torch.uint8).cuda()[lo:hi]
+        assert t.data_ptr() % 16 == lead % 16 and t.numel() == len(text.buf)
+        odd = t if odd is None else odd
+        sc = _scanner(row, text, exp["nlines"])
+        try:
+            res = sc.scan_tensor(pat, t, row.options, row.want)
+            got = sc.last_plan()
+            assert sc.last_runs() == 1, ("runs", sc.last_runs(), "fallback", sc.fallback(), K.instance_key(got, row.options, row.want))
+            assert K.instance_key(got, row.options, row.want) == row.key
+            assert got == plan, (got, plan)
+            SEEN.setdefault(sc.last_kernel(), set()).add(lead - W.GUARD)
+            _compare("lead %d" % lead, sc, res, exp, exp_all, row.want, offsets)
+        finally:
+            sc.close()
+    monkeypatch.setenv("SEEQ_SEGMENT_BYTES", "65536")
+    sc = _scanner(row, text, exp["nlines"])
+    try:
+        res = sc.scan_tensor(pat, odd, row.options, row.want)
+        got, runs, fallback = sc.last_plan(), sc.last_runs(), sc.fallback()
+        assert K.instance_key(got, row.options, row.want) == row.key, (runs, fallback)
+        if plan["window_ok"] and runs != 1:
+            assert runs == 2 and fallback[0] == OVF_SEAM, (runs, fallback)      # (as in test_instance_against_the_oracle)
+            assert got == dict(plan, window_ok=0), (got, plan)
+        else:
+            assert runs == 1, ("runs", runs, "fallback", fallback)
+            assert got == plan, (got, plan)
+        _compare("lead %d, 64 KiB segments" % W.odd_lead(i), sc, res, exp, exp_all, row.want, offsets)
+    finally:
+        sc.close()
+
+
+def test_every_scan_kernel_ran_at_small_and_at_large_odd_leads():
+    """Closes test_instance_on_a_hostile_window: each scan kernel was seen at an odd lead below 16 and at one above 64 (modulo 4096)."""
+    for kernel in ("k_forward", "k_direct", "k_stream", "k_pair", "k_myers"):
+        leads = SEEN.get(kernel, set())
+        assert any(r % 2 and r < 16 for r in leads) and any(r % 2 and r > 64 for r in leads), (kernel, sorted(leads))
 
 
 def test_last_plan_after_a_fallback_rerun_is_the_reruns_plan(gpu, capi, shared, monkeypatch):
