@@ -209,7 +209,7 @@ def _same_scan(s, res, exp, offs, records=True):
 
 
 # ---- the families ----
-def _scans(sc, view, ref, pats):
+def _scans(sc, view, ref, pats, fresh=None):
     from seeq_amd import device as dev
     t = view.tensor()
     what = view.name
@@ -217,24 +217,24 @@ def _scans(sc, view, ref, pats):
         exp = ref.scan("A", mode)
         assert len(exp["records"]) > (50 if "front" not in what else -1)
         _go(sc, "%s: scan, mode %d" % (what, mode), lambda s: s.scan_tensor(pats["A"], t, _opt(view, mode), dev.WANT_RECORDS),
-            lambda s, res: _same_scan(s, res, exp, ref.offs))
+            lambda s, res: _same_scan(s, res, exp, ref.offs), fresh)
     exp = ref.scan("A", SQ_ALL)
     _go(sc, what + ": line count", lambda s: s.scan_tensor(pats["A"], t, _opt(view, SQ_FIRST), dev.WANT_COUNTLINES),
-        lambda s, res: _same_scan(s, res, exp, ref.offs, records=False))
+        lambda s, res: _same_scan(s, res, exp, ref.offs, records=False), fresh)
     if not view.fastq:                                      # (the multi-pattern entries refuse SEEQDEV_FASTQ)
         def multi(s, got):
             for name, g in zip(FLANKS, got):
                 e = ref.scan(name, SQ_BEST)
                 assert g["nlines"] == e["nlines"] and g["nmatchlines"] == e["nmatchlines"], name
                 assert np.array_equal(g["records"].astype(np.uint64), e["records"]), name
-        _go(sc, what + ": four patterns", lambda s: s.scan_tensor_multi(list(pats.values()), t, SQ_BEST, dev.WANT_RECORDS), multi)
-    _go(sc, what + ": demux", lambda s: s.demux_tensor(list(pats.values()), t, _opt(view, SQ_BEST)), lambda s, res: _same_demux(res, ref.demux()))
+        _go(sc, what + ": four patterns", lambda s: s.scan_tensor_multi(list(pats.values()), t, SQ_BEST, dev.WANT_RECORDS), multi, fresh)
+    _go(sc, what + ": demux", lambda s: s.demux_tensor(list(pats.values()), t, _opt(view, SQ_BEST)), lambda s, res: _same_demux(res, ref.demux()), fresh)
     for mode in (SQ_ALL, SQ_BEST):
         _go(sc, "%s: both strands, mode %d" % (what, mode), lambda s: s.strands_tensor(pats["A"], t, _opt(view, mode), dev.WANT_RECORDS),
-            lambda s, res: _same_strands(s, res, ref.strands("A", mode), ref.offs))
+            lambda s, res: _same_strands(s, res, ref.strands("A", mode), ref.offs), fresh)
 
 
-def _inserts(sc, view, ref, pats):
+def _inserts(sc, view, ref, pats, fresh=None):
     t = view.tensor()
     for pair, mode, window in INSERT_CASES:
         rows = ref.rows(pair, mode, window)
@@ -243,7 +243,7 @@ def _inserts(sc, view, ref, pats):
             _same_inserts(s, res, ref.joined(pair, mode), window, ref.offs)
             assert s.insert_text(t).cpu().numpy().tobytes() == _host_text(view.window, rows, ref.offs)
         _go(sc, "%s: inserts %s, mode %d, window %s" % (view.name, pair, mode, window),
-            lambda s: s.inserts_tensor(pats[pair[0]], pats[pair[1]], t, _opt(view, mode), *window), check)
+            lambda s: s.inserts_tensor(pats[pair[0]], pats[pair[1]], t, _opt(view, mode), *window), check, fresh)
 
 
 def _cut(s, view, ref, pats, pair):
@@ -257,7 +257,7 @@ def _cut(s, view, ref, pats, pair):
     return rows
 
 
-def _tallies(sc, view, ref, pats):
+def _tallies(sc, view, ref, pats, fresh=None):
     """tally from inserts and from hits; hold + grouped; the collapse under both rules"""
     from seeq_amd import device as dev
     t = view.tensor()
@@ -267,14 +267,14 @@ def _tallies(sc, view, ref, pats):
     def from_inserts(s):
         _cut(s, view, ref, pats, "AB")
         return s.tally(t)
-    _go(sc, view.name + ": tally of inserts", from_inserts, lambda s, res: _same_tally(res, [b for _, b in guides]))
+    _go(sc, view.name + ": tally of inserts", from_inserts, lambda s, res: _same_tally(res, [b for _, b in guides]), fresh)
     hits = ref.spans([(r[0], r[1], r[2]) for r in ref.hit_rows("A")])
 
     def from_hits(s):
         res = s.scan_tensor(pats["A"], t, _opt(view, SQ_BEST), dev.WANT_RECORDS)
         _same_scan(s, res, ref.scan("A", SQ_BEST), ref.offs)
         return s.tally(t, source="hits")
-    _go(sc, view.name + ": tally of hits", from_hits, lambda s, res: _same_tally(res, [b for _, b in hits]))
+    _go(sc, view.name + ": tally of hits", from_hits, lambda s, res: _same_tally(res, [b for _, b in hits]), fresh)
     held, hcnt = _held_of(guides)
 
     def grouped(s):
@@ -291,10 +291,10 @@ def _tallies(sc, view, ref, pats):
         exp = ref._once("collapse", lambda: _restated(pairs))
         for rule in RULE_NAMES:
             _same_collapse(col[rule], pairs, groups, exp, rule, res["max_len"])
-    _go(sc, view.name + ": hold, grouped, collapse", grouped, check)
+    _go(sc, view.name + ": hold, grouped, collapse", grouped, check, fresh)
 
 
-def _library(sc, view, ref, pats, chain):
+def _library(sc, view, ref, pats, chain, fresh=None):
     t = view.tensor()
     lib = PyLibrary(chain.guides)
     guides, umis = ref.spans(ref.rows("AB")), ref.spans(ref.rows("CD"))
@@ -307,7 +307,7 @@ def _library(sc, view, ref, pats, chain):
     def check(s, res):
         cnt = _same_library(res, lib, [b for _, b in guides], 1)
         assert "front" in view.name or (cnt["ncorrected"] > 20 and cnt["nunknown"] > 5)
-    _go(sc, view.name + ": library tally", counted, check)
+    _go(sc, view.name + ": library tally", counted, check, fresh)
 
     def held(s):
         _cut(s, view, ref, pats, "AB")
@@ -320,10 +320,10 @@ def _library(sc, view, ref, pats, chain):
         cnt, _, ids = lib.tally([b for _, b in guides], 1)
         assert {k: hold[k] for k in cnt if k != "ndistinct"} == {k: v for k, v in cnt.items() if k != "ndistinct"}
         _same_grouped(res, [(ln, i) for (ln, _), i in zip(guides, ids)], umis)
-    _go(sc, view.name + ": library hold, grouped", held, check_held)
+    _go(sc, view.name + ": library hold, grouped", held, check_held, fresh)
 
 
-def _gate(sc, view, ref, pats):
+def _gate(sc, view, ref, pats, fresh=None):
     """quality_gate from both sources, then tally and grouped tally over the gated spans"""
     from seeq_amd import device as dev
     t = view.tensor()
@@ -345,7 +345,7 @@ def _gate(sc, view, ref, pats):
         _same_gate(g, gkinds, gcnt, *src)
         _same_tally(tl, [b for _, b in gspans])
         got["kinds"] = g["kinds"].tolist()
-    _go(sc, view.name + ": gate of inserts, tally of the gated", inserts, check)
+    _go(sc, view.name + ": gate of inserts, tally of the gated", inserts, check, fresh)
     hrows = ref.hit_rows("B")
     hkinds, hcnt = ref.gate(hrows)
 
@@ -354,7 +354,7 @@ def _gate(sc, view, ref, pats):
         _same_scan(s, res, ref.scan("B", SQ_BEST), ref.offs)
         rec, off = s.records(len(hrows)), s.record_offsets(len(hrows))
         return s.quality_gate(t, source="hits"), rec, off
-    _go(sc, view.name + ": gate of hits", hits, lambda s, tr: _same_gate(tr[0], hkinds, hcnt, tr[1], tr[2]))
+    _go(sc, view.name + ": gate of hits", hits, lambda s, tr: _same_gate(tr[0], hkinds, hcnt, tr[1], tr[2]), fresh)
     held, hold_cnt = _held_of(gspans)
 
     def grouped(s):
@@ -369,7 +369,7 @@ def _gate(sc, view, ref, pats):
         g, hold, u, res = tr
         assert g["npassed"] == len(gspans) and u["npassed"] == len(uspans) and hold == hold_cnt
         _same_grouped(res, held, uspans)
-    _go(sc, view.name + ": hold gated, members gated", grouped, check_grouped)
+    _go(sc, view.name + ": hold gated, members gated", grouped, check_grouped, fresh)
     return gkinds, ukinds
 
 
@@ -418,39 +418,79 @@ def test_quality_gate(gpu, capi, setup, pats, name, monkeypatch):
     sc.close()
 
 
-def test_packed_reads_between_guards(gpu, capi, oracle, monkeypatch):
-    """pack_reads_device + run_packed: fixed-length reads as a window at an odd lead, the guards holding reads with occurrences."""
+class PackedCase:
+    """pack_reads_device + run_packed: fixed-length reads as a window at an odd lead, the guards holding reads with occurrences.  `t`: the
+    window on the device, `pb` / `pn`: room for its packed bases and N mask, zeroed; `exp`: the ASCII oracle over the window."""
+
+    def __init__(self, oracle):
+        import torch
+        from seeq_amd import device as dev
+        self.expr, self.tau, self.L, self.n = expr, tau, L, n = "GATGTAGCGCGATTAGCCTG", 3, 150, 2051
+        self.window = window = bytes(oracle.synth_reads(0, n, L, expr, tau))
+        read = (b"ACGT" * 40)[:L - 20] + expr.encode() + b"\n"
+        assert len(read) == L + 1 and len(window) == n * (L + 1)
+        big, lo, hi = W.place(window, W.GUARD + 11, read * 3, read * 3)
+        self.exp = exp = oracle.buffer_scan(expr, tau, window, SQ_BEST)
+        ext = oracle.buffer_scan(expr, tau, read * 3 + window + read * 3, SQ_BEST)
+        assert ext["nmatchlines"] == exp["nmatchlines"] + 6 and len(exp["records"]) > 50
+        self.t = torch.frombuffer(bytearray(big), dtype=torch.uint8).cuda()[lo:hi]
+        self.pb = torch.zeros(n * ((L + 3) // 4), dtype=torch.uint8, device="cuda")
+        self.pn = torch.zeros(n * ((L + 7) // 8), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        self.pat = dev.Pattern(expr, tau)
+
+    def pack(self, stream=None):
+        from seeq_amd import device as dev
+        dev.pack_reads_device(self.t.data_ptr(), self.n, self.L, self.pb.data_ptr(), self.pn.data_ptr(), stream=stream)
+
+    def packed_as_on_the_host(self):
+        from seeq_amd import device as dev
+        hb, hn, hcount = dev.pack_reads(self.window, self.L)
+        assert hcount == self.n and self.pb.cpu().numpy().tobytes() == hb.tobytes() and self.pn.cpu().numpy().tobytes() == hn.tobytes()
+
+    def scan(self, s):
+        from seeq_amd import device as dev
+        s.run_packed(self.pat, self.pb.data_ptr(), self.pn.data_ptr(), self.n, self.L, options=SQ_BEST, want=dev.WANT_RECORDS)
+
+    def same(self, s, res, exp=None):
+        exp = exp or self.exp
+        assert res["nlines"] == self.n and res["nmatchlines"] == exp["nmatchlines"] and res["nrecords"] == len(exp["records"])
+        assert np.array_equal(s.records(res["nrecords"]).astype(np.uint64), exp["records"])
+
+    def close(self):
+        self.pat.close()
+
+
+def _packed_reads(case, scanner, stream=None, late=None):
+    """scanner(): the context; stream: the hipStream_t (int) the packing runs on (None: the null stream).  late(case), when given
+    (tests/late_text.py), is called in front of the packing: it makes the window AND the packed arrays late on the stream -- the packing
+    and the packed scan then follow each other with no host wait between them, and the packed arrays are held against the host's
+    behind the fetch."""
     import torch
-    from seeq_amd import device as dev
-    expr, tau, L, n = "GATGTAGCGCGATTAGCCTG", 3, 150, 2051
-    window = bytes(oracle.synth_reads(0, n, L, expr, tau))
-    read = (b"ACGT" * 40)[:L - 20] + expr.encode() + b"\n"
-    assert len(read) == L + 1 and len(window) == n * (L + 1)
-    big, lo, hi = W.place(window, W.GUARD + 11, read * 3, read * 3)
-    exp = oracle.buffer_scan(expr, tau, window, SQ_BEST)
-    ext = oracle.buffer_scan(expr, tau, read * 3 + window + read * 3, SQ_BEST)
-    assert ext["nmatchlines"] == exp["nmatchlines"] + 6 and len(exp["records"]) > 50
-    t = torch.frombuffer(bytearray(big), dtype=torch.uint8).cuda()[lo:hi]
-    pb = torch.zeros(n * ((L + 3) // 4), dtype=torch.uint8, device="cuda")
-    pn = torch.zeros(n * ((L + 7) // 8), dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    pat = dev.Pattern(expr, tau)
-    sc = dev.Scanner()
+    sc = scanner()
 
     def call(s):
-        dev.pack_reads_device(t.data_ptr(), n, L, pb.data_ptr(), pn.data_ptr())
-        torch.cuda.synchronize()
-        hb, hn, hcount = dev.pack_reads(window, L)
-        assert hcount == n and pb.cpu().numpy().tobytes() == hb.tobytes() and pn.cpu().numpy().tobytes() == hn.tobytes()
-        s.run_packed(pat, pb.data_ptr(), pn.data_ptr(), n, L, options=SQ_BEST, want=dev.WANT_RECORDS)
-        return s.fetch()
-
-    def check(s, res):
-        assert res["nlines"] == n and res["nmatchlines"] == exp["nmatchlines"] and res["nrecords"] == len(exp["records"])
-        assert np.array_equal(s.records(res["nrecords"]).astype(np.uint64), exp["records"])
-    _go(sc, "packed reads at an odd lead", call, check)
+        if late is not None:
+            late(s, case)
+        case.pack(stream)
+        if late is None:
+            torch.cuda.synchronize()
+            case.packed_as_on_the_host()
+        case.scan(s)
+        res = s.fetch()
+        if late is not None:
+            torch.cuda.synchronize()
+            case.packed_as_on_the_host()
+        return res
+    _go(sc, "packed reads at an odd lead", call, case.same, scanner)
     sc.close()
-    pat.close()
+
+
+def test_packed_reads_between_guards(gpu, capi, oracle, monkeypatch):
+    from seeq_amd import device as dev
+    case = PackedCase(oracle)
+    _packed_reads(case, dev.Scanner)
+    case.close()
 
 
 # ---- the guards are live: the same entries over window + guard bytes give the reference's answer over THOSE bytes, another one ----
