@@ -452,8 +452,10 @@ int seeqdevTallyDecode(uint64_t key, char out[32]);
  *                            replaces it (a failed hold leaves none).  A hold over zero records is a valid, empty column.
  *   seeqdevScanTallyGrouped  pairs the spans of SEEQDEV_TALLY_INSERTS or SEEQDEV_TALLY_HITS (anything else: EINVAL) -- the MEMBERS -- with
  *                            the held column by line and counts the distinct pairs.  EINVAL without a completed hold, before any device
- *                            call.  THE CALLER KEEPS THE LINE NUMBERING OF THE TWO CALLS THE SAME: SEEQDEV_FASTQ in both scans or in
- *                            neither, over the same buffer.
+ *                            call.  THE CALLER KEEPS THE LINE NUMBERING OF THE CALLS THE SAME: SEEQDEV_FASTQ in every scan or in none,
+ *                            over buffers whose lines (records) number alike.  Each call takes its own text, so the held column, an
+ *                            appended column (below) and the members may each come from a different buffer -- read 1 and read 2 of a
+ *                            paired run, both under SEEQDEV_FASTQ: record k of one is record k of the other.
  *   group of a line          the key of the FIRST held record with that line number (a lower-bound search: several hits of a line under
  *                            SQ_ALL, the first one decides); 0 when the line has no held record or that record has no key.
  *   pair                     a member span with key m on a line of group g != 0 is the pair (g, m).  Every other span is counted in
@@ -620,6 +622,60 @@ typedef struct {
 int seeqdevScanSetLibrary(seeqdev_scan_t * scan, const uint64_t * keys, size_t n, int max_mismatch);
 int seeqdevScanTallyLibrary    (seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_library_counts_t * counts);
 int seeqdevScanTallyHoldLibrary(seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_library_counts_t * counts);
+
+/* KEY COLUMNS APPENDED TO THE HELD COLUMN: (CELL, GUIDE) x UMI.  Counting pipelines carry three or more keys per read -- cell barcode x
+ * guide x UMI, sample x guide x UMI -- and everything behind the hold works on ONE 64-bit group word.  An append composes that word from
+ * several columns ON THE DEVICE (seeq_tally_append.h); seeqdevScanTallyGrouped, seeqdevScanTallyCollapse, SEEQDEV_TALLY_GATED and the library
+ * then apply unchanged: the groups are the tuples.
+ *   seeqdevScanTallyHoldAppend  builds a second column N from `source` exactly as seeqdevScanTallyHold would (SEEQDEV_TALLY_INSERTS, _HITS,
+ *                            _GATED, _DEMUX: the same per-record line and key, kinds, counts and EINVAL / EIO / E2BIG cases; *column is
+ *                            what that hold returns) in arrays of its own.  Its WIDTH w = column->key_bits: the bit length of its largest
+ *                            key, 0 when no record has one.  Then every held record i is rewritten in place:
+ *                            k = the key of the FIRST record of N on the line of i (0: the line has none, or that record has no key);
+ *                            key[i] = key[i] != 0 && k != 0 ? (key[i] << w) | k : 0.  Lines, record count and order do not change.  A
+ *                            held record that had a key and loses it is DROPPED: nbefore = nheld + ndropped.
+ *   seeqdevScanTallyHoldAppendLibrary  the same with the new column assigned to the context's library as seeqdevScanTallyHoldLibrary
+ *                            assigns (sources SEEQDEV_TALLY_INSERTS, _HITS, _GATED; SEEQDEV_TALLY_DEMUX and a context without a library:
+ *                            EINVAL): k is the entry's id, w = bitlen(N) of the library; *column is what that hold returns.
+ *   key_bits                 afterwards the bit length of the largest composed key, computed on the device (0: nothing is left): what a
+ *                            following seeqdevScanTallyGrouped takes its group passes from.
+ *   THE WORD                 is injective over its columns (k < 2^w: the shift loses nothing) and COLUMN-MAJOR: in the group table's
+ *                            order column 0 -- the hold's -- is most significant, then column 1, and so on.  seeqdevScanTallyHoldColumns
+ *                            serves the widths, seeqdevTallySplit takes a group word apart with them (host only, no GPU).
+ *   limits                   the widths sum to at most 63 bits: key_bits + w > 63 is E2BIG (the message names both numbers), decided
+ *                            after N is built and before the held column is touched -- it is what it was.  A 16-base barcode (33 bits)
+ *                            and a guide id (17) fit; two raw 20-base columns (41 + 41) do not: that is what the library ids are for.
+ *                            At most 8 columns: a ninth append is EINVAL.  Column 0's width is the hold's key_bits at the time of the hold.
+ *   w == 0                   is a valid result: every key becomes 0, nheld = 0, a following grouped call pairs nothing.
+ * EINVAL, before any device call: a NULL scan, column or counts, an unknown source, a context without a completed hold (or library), a
+ * ninth column, and the source's own cases.  Those, E2BIG and an EIO while N is built (a span outside its text) leave the held column and
+ * its columns as they were; a device failure during the join leaves no column, as a failed hold does.  EIO after the join: an internal
+ * inconsistency (the message names the numbers).  A new hold resets to one column.  Synchronous.
+ * seeqdevScanCopyHeld copies records [first, first + n) of the held column -- line numbers and keys, either pointer may be NULL -- with the
+ * bounds of every seeqdevScanCopy* entry (EINVAL beyond the held records; a context without a column has none).
+ * Device memory of its own: 12 bytes per appended record (line, key) plus 32 per tile of 1 024, one group, freed with the context; the
+ * library variant's miss indices lie where seeqdevScanTallyHoldLibrary's do.  (The reference counts nothing: an addition of this boundary.) */
+typedef struct {
+   uint64_t nrecords;   /* records of the held column (unchanged by the call) */
+   uint64_t nbefore;    /* of them, with a key before the call */
+   uint64_t nheld;      /* with a key after it */
+   uint64_t ndropped;   /* nbefore - nheld */
+   uint32_t width;      /* bits the appended column took */
+   uint32_t key_bits;   /* bit length of the largest composed key; 0: none */
+   uint32_t ncolumns;   /* columns of the held key now */
+   uint32_t reserved;   /* 0 */
+} seeqdev_tally_append_counts_t;   /* 48 bytes */
+
+int seeqdevScanTallyHoldAppend       (seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes,
+                                      seeqdev_tally_hold_counts_t * column, seeqdev_tally_append_counts_t * counts);
+int seeqdevScanTallyHoldAppendLibrary(seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes,
+                                      seeqdev_tally_library_counts_t * column, seeqdev_tally_append_counts_t * counts);
+/* the widths of the held key's columns, column 0 first: returns their number (0: no column) and fills min(cap, ncolumns) of them */
+int seeqdevScanTallyHoldColumns(const seeqdev_scan_t * scan, uint32_t * widths, int cap);
+int seeqdevScanCopyHeld(seeqdev_scan_t * scan, uint32_t * lines_out, uint64_t * keys_out, size_t first, size_t n);
+/* out[c], c < ncolumns: the key of column c in a group word.  -1 / EINVAL: 0 columns or more than 8, widths that sum to more than 63, a key
+ * with bits above them, a NULL pointer. */
+int seeqdevTallySplit(uint64_t key, const uint32_t * widths, int ncolumns, uint64_t * out);
 
 /* THE BASE-QUALITY GATE -- every FASTQ counting pipeline puts a bar on the base qualities of what it counts ("drop the UMI if any base is
  * below Q", "at most k bases below Q in the barcode"): an uncertain base is what makes the spurious distinct keys, the corrected library

@@ -126,6 +126,12 @@ class seeqdev_tally_library_counts_t(C.Structure):
                 ("passes", C.c_uint32)]
 
 
+class seeqdev_tally_append_counts_t(C.Structure):
+    _fields_ = [("nrecords", C.c_uint64), ("nbefore", C.c_uint64), ("nheld", C.c_uint64), ("ndropped", C.c_uint64), ("width", C.c_uint32),
+                ("key_bits", C.c_uint32), ("ncolumns", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SEEQDEV_TALLY_COLUMNS = 8           # columns of a held key, the hold's own included
 SEEQDEV_TALLY_GATED = 4             # the spans the context's last quality gate passed
 SEEQDEV_QGATE_PASS, SEEQDEV_QGATE_LOW, SEEQDEV_QGATE_LONG, SEEQDEV_QGATE_FAR, SEEQDEV_QGATE_MISFIT = 0, 1, 2, 3, 4
 
@@ -160,6 +166,7 @@ EXPORTS = [
     "seeqdevScanTallyCollapse", "seeqdevScanTallyParentsDevice", "seeqdevScanTallyCollapseDevice", "seeqdevScanCopyTallyParents",
     "seeqdevScanCopyTallyCollapse", "seeqdevScanLastTallyCollapseMs",
     "seeqdevScanSetLibrary", "seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary",
+    "seeqdevScanTallyHoldAppend", "seeqdevScanTallyHoldAppendLibrary", "seeqdevScanTallyHoldColumns", "seeqdevScanCopyHeld", "seeqdevTallySplit",
     "seeqdevScanQualityGate", "seeqdevScanGatedDevice", "seeqdevScanCopyGated", "seeqdevScanCopyGatedOffsets", "seeqdevScanCopyGateKinds",
     "seeqdevScanLastQualityGateMs",
     "seeqdevScanLastRuns", "seeqdevScanFallback", "seeqdevScanLastPlan",
@@ -363,6 +370,16 @@ def lib():
     for name in ("seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary"):
         getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(seeqdev_tally_library_counts_t)]
         getattr(L, name).restype = C.c_int
+    L.seeqdevScanTallyHoldAppend.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(seeqdev_tally_hold_counts_t), P(seeqdev_tally_append_counts_t)]
+    L.seeqdevScanTallyHoldAppend.restype = C.c_int
+    L.seeqdevScanTallyHoldAppendLibrary.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(seeqdev_tally_library_counts_t), P(seeqdev_tally_append_counts_t)]
+    L.seeqdevScanTallyHoldAppendLibrary.restype = C.c_int
+    L.seeqdevScanTallyHoldColumns.argtypes = [C.c_void_p, P(C.c_uint32), C.c_int]
+    L.seeqdevScanTallyHoldColumns.restype = C.c_int
+    L.seeqdevScanCopyHeld.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+    L.seeqdevScanCopyHeld.restype = C.c_int
+    L.seeqdevTallySplit.argtypes = [C.c_uint64, P(C.c_uint32), C.c_int, P(C.c_uint64)]
+    L.seeqdevTallySplit.restype = C.c_int
     L.seeqdevScanQualityGate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(seeqdev_qgate_counts_t)]
     L.seeqdevScanQualityGate.restype = C.c_int
     L.seeqdevScanGatedDevice.argtypes = [C.c_void_p]

@@ -23,7 +23,8 @@
  * Here: plumbing, pattern handle, scan context, the segment and packed drivers, the scan
  * entries.  The side entries are included where they belong in that order: seeq_synth.h,
  * seeq_text_alloc.h, seeq_multi_host.h, seeq_demux_host.h, seeq_strand_host.h, seeq_insert_host.h,
- * seeq_tally_host.h, seeq_tally_group_host.h, seeq_tally_library_host.h, seeq_tally_collapse_host.h, seeq_string.h.
+ * seeq_tally_host.h, seeq_tally_group_host.h, seeq_tally_library_host.h (and behind it seeq_tally_append_host.h), seeq_tally_collapse_host.h,
+ * seeq_string.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -112,6 +113,7 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_insert.h"
 #include "seeq_tally.h"
 #include "seeq_tally_group.h"
+#include "seeq_tally_append.h"
 #include "seeq_tally_library.h"
 #include "seeq_tally_collapse.h"
 #include "seeq_qgate.h"
@@ -564,7 +566,11 @@ struct seeqdev_scan {
    size_t    th_n;                                        /* held records */
    uint32_t  th_key_bits;                                 /* bits of the largest held key */
    bool      th_done;                                     /* a hold has completed: th_n records (none included) are a column */
-   bool      dm_done;                                     /* a demux has completed: dm_nrec records (none included) are a result */
+   /* seeqdevScanTallyHoldAppend (seeq_tally_append.h): the held key's columns, and the arrays a new column is built in before it is joined */
+   uint64_t  th_nkeyed;                                   /* held records with a key */
+   uint32_t  th_width[SEEQ_TALLY_COLUMNS]; uint32_t th_ncol;      /* the widths of the held key's columns, column 0 (the hold's) first */
+   uint32_t *ta_line; uint64_t *ta_key; uint32_t *ta_stat; size_t cap_ta;      /* per appended record: line, key; per tile: its hold's eight words */
+   bool      dm_done;                                    /* a demux has completed: dm_nrec records (none included) are a result */
    uint64_t *tg_g0, *tg_g1; uint32_t *tg_sum, *tg_stat; size_t cap_tg;         /* per span: the two group-word arrays; per tile: the head sums, the pack's words */
    seeqdev_tally_pair_t *tg_pairs; size_t cap_tg_pairs;   /* the pair table: one entry per distinct (group, member) */
    seeqdev_tally_group_t *tg_groups; size_t cap_tg_groups;      /* the group table: one entry per distinct group */

@@ -29,9 +29,17 @@ static int tally_group_outside(const char *who, size_t nbytes)
    return -1;
 }
 
-/* The held column of the n records rec / off (demux: seeqdev_demux_t records, no offsets, no text).  Waits. */
+/* The arrays a hold writes: the context's held column (th_line / th_key / th_stat), or the column an append builds beside it
+   (seeq_tally_append_host.h) -- one capacity group either way. */
+struct TallyHoldTarget {
+   uint32_t *&line; uint64_t *&key; uint32_t *&stat; size_t &cap;
+};
+
+static TallyHoldTarget tally_hold_target(seeqdev_scan *s) { return {s->th_line, s->th_key, s->th_stat, s->cap_th}; }
+
+/* The column of the n records rec / off (demux: seeqdev_demux_t records, no offsets, no text) in the arrays of `to`.  Waits. */
 static int tally_hold_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uint32_t n, bool demux, const void *d_text, size_t nbytes,
-                          seeqdev_tally_hold_counts_t *counts)
+                          seeqdev_tally_hold_counts_t *counts, const TallyHoldTarget &to)
 {
    const hipStream_t st = s->stream;
    memset(counts, 0, sizeof *counts);
@@ -39,18 +47,18 @@ static int tally_hold_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off
    if (!n) return 0;                                       /* no records: nothing is launched, the column is empty */
    const size_t nt = (size_t)tally_tiles(n);
    if (tally_group_ws_cnt(s)) return -1;
-   if (ws_grow(&s->ws, &s->cap_th, n, {{s->th_line, n * sizeof(uint32_t)}, {s->th_key, n * sizeof(uint64_t)},
-                                       {s->th_stat, nt * SEEQ_TALLY_STAT * sizeof(uint32_t)}})) return -1;
+   if (ws_grow(&s->ws, &to.cap, n, {{to.line, n * sizeof(uint32_t)}, {to.key, n * sizeof(uint64_t)},
+                                    {to.stat, nt * SEEQ_TALLY_STAT * sizeof(uint32_t)}})) return -1;
    TallyGroupArgs a;
    memset(&a, 0, sizeof a);
    a.rec = rec; a.off = off; a.n = n; a.nt = (uint32_t)nt;
    a.text = (const uint8_t *)d_text; a.nbytes = nbytes;
    a.demux = demux ? 1u : 0u;
-   a.hold_line = s->th_line; a.hold_key = s->th_key;
-   a.tstat = s->th_stat;
+   a.hold_line = to.line; a.hold_key = to.key;
+   a.tstat = to.stat;
    a.cnt = s->d_tgcnt;
-   if ((size_t)n > s->cap_th || tally_tiles(s->cap_th) < nt) {
-      snprintf(g_last_error, sizeof g_last_error, "tally hold: %u records, arrays for %zu", n, s->cap_th);
+   if ((size_t)n > to.cap || tally_tiles(to.cap) < nt) {
+      snprintf(g_last_error, sizeof g_last_error, "tally hold: %u records, arrays for %zu", n, to.cap);
       errno = EIO;
       return -1;
    }
@@ -68,36 +76,62 @@ static int tally_hold_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off
    return 0;
 }
 
-extern "C" int seeqdevScanTallyHold(seeqdev_scan_t *s, int source, const void *d_text, size_t nbytes, seeqdev_tally_hold_counts_t *counts)
+/* What a hold over `source` does first: SEEQDEV_TALLY_DEMUX names the records seeqdevScanDemuxDevice serves now (no text, no offsets), every
+   other source is tally_enter's; `missing` as there. */
+static int tally_hold_enter(seeqdev_scan *s, const void *counts, int source, const char *missing, const void **d_text, size_t *nbytes, const uint4 **rec,
+                            const uint64_t **off, uint64_t *n)
 {
-   const bool demux = source == SEEQDEV_TALLY_DEMUX;
-   const uint4 *rec;
-   const uint64_t *off = NULL;
-   uint64_t n;
-   if (demux) {
-      seeqerr = 0;
-      if (!s || !counts) { errno = EINVAL; return -1; }
-      /* what seeqdevScanDemuxDevice serves: valid until the context's next scan -- a demux leaves nothing to fetch (scan_forget), a plain or
-         packed scan after it leaves its pattern */
-      if (!s->dm_done || s->pat || s->ran) {
-         snprintf(g_last_error, sizeof g_last_error, "tally hold: %s", !s->dm_done ? "the context holds no result of a demux call" : "a later scan has invalidated the demux records");
-         errno = EINVAL;
-         return -1;
-      }
-      rec = s->dm_out; n = s->dm_nrec;
-      d_text = NULL; nbytes = 0;
-      if (n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
-      if (use_device(s->device)) return -1;
-   } else if (tally_enter(s, counts, source, NULL, &d_text, &nbytes, &rec, &off, &n)) {
+   if (source != SEEQDEV_TALLY_DEMUX) return tally_enter(s, counts, source, missing, d_text, nbytes, rec, off, n);
+   seeqerr = 0;
+   if (!s || !counts) { errno = EINVAL; return -1; }
+   if (missing) {
+      snprintf(g_last_error, sizeof g_last_error, "%s", missing);
+      errno = EINVAL;
       return -1;
    }
-   s->th_done = false;                                     /* (the column of the hold before is gone, whatever comes of this one) */
+   /* what seeqdevScanDemuxDevice serves: valid until the context's next scan -- a demux leaves nothing to fetch (scan_forget), a plain or
+      packed scan after it leaves its pattern */
+   if (!s->dm_done || s->pat || s->ran) {
+      snprintf(g_last_error, sizeof g_last_error, "tally hold: %s", !s->dm_done ? "the context holds no result of a demux call" : "a later scan has invalidated the demux records");
+      errno = EINVAL;
+      return -1;
+   }
+   *rec = s->dm_out; *off = NULL; *n = s->dm_nrec;
+   *d_text = NULL; *nbytes = 0;
+   if (*n > 0xFFFFFFFFull) { errno = E2BIG; return -1; }
+   return use_device(s->device);
+}
+
+/* the column of the hold before is gone, whatever comes of the one that begins */
+static void tally_hold_reset(seeqdev_scan *s)
+{
+   s->th_done = false;
    s->th_n = 0;
    s->th_key_bits = 0;
-   if (tally_hold_run(s, rec, off, (uint32_t)n, demux, d_text, nbytes, counts)) return -1;
+   s->th_nkeyed = 0;
+   s->th_ncol = 0;
+}
+
+/* a hold has completed: n records, nkeyed of them with a key, the largest of key_bits bits -- one column of that width */
+static void tally_hold_done(seeqdev_scan *s, uint64_t n, uint64_t nkeyed, uint32_t key_bits)
+{
    s->th_n = (size_t)n;
-   s->th_key_bits = counts->key_bits;
+   s->th_key_bits = key_bits;
+   s->th_nkeyed = nkeyed;
+   s->th_ncol = 1;
+   s->th_width[0] = key_bits;
    s->th_done = true;
+}
+
+extern "C" int seeqdevScanTallyHold(seeqdev_scan_t *s, int source, const void *d_text, size_t nbytes, seeqdev_tally_hold_counts_t *counts)
+{
+   const uint4 *rec;
+   const uint64_t *off;
+   uint64_t n;
+   if (tally_hold_enter(s, counts, source, NULL, &d_text, &nbytes, &rec, &off, &n)) return -1;
+   tally_hold_reset(s);
+   if (tally_hold_run(s, rec, off, (uint32_t)n, source == SEEQDEV_TALLY_DEMUX, d_text, nbytes, counts, tally_hold_target(s))) return -1;
+   tally_hold_done(s, n, counts->nheld, counts->key_bits);
    return 0;
 }
 

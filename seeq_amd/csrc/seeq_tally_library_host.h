@@ -177,11 +177,9 @@ extern "C" int seeqdevScanTallyHoldLibrary(seeqdev_scan_t *s, int source, const 
    const uint64_t *off;
    uint64_t n;
    if (tally_enter(s, counts, source, tally_library_missing(s), &d_text, &nbytes, &rec, &off, &n)) return -1;
-   s->th_done = false;                                     /* (the column of the hold before is gone, whatever comes of this one) */
-   s->th_n = 0;
-   s->th_key_bits = 0;
+   tally_hold_reset(s);
    seeqdev_tally_hold_counts_t held;
-   if (tally_hold_run(s, rec, off, (uint32_t)n, false, d_text, nbytes, &held)) return -1;
+   if (tally_hold_run(s, rec, off, (uint32_t)n, false, d_text, nbytes, &held, tally_hold_target(s))) return -1;
    memset(counts, 0, sizeof *counts);
    counts->nspans = n;
    counts->key_bits = tally_lib_bitlen(s->lb_n);
@@ -200,10 +198,10 @@ extern "C" int seeqdevScanTallyHoldLibrary(seeqdev_scan_t *s, int source, const 
    tally_library_counts(counts, l);
    if (counts->nexact + counts->ncorrected + counts->nambiguous + counts->nunknown + counts->nlong + counts->nforeign != n)
       return tally_library_fail("hold", l, TallyCnt{}, (uint32_t)n, held.nheld, counts->nassigned, s->lb_n);
-   s->th_n = (size_t)n;
-   s->th_key_bits = counts->key_bits;
-   s->th_done = true;
+   tally_hold_done(s, n, counts->nassigned, counts->key_bits);
    return 0;
 }
+
+#include "seeq_tally_append_host.h"
 
 #endif

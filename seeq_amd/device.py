@@ -478,7 +478,7 @@ class Scanner:
     def tally_grouped(self, t=None, source="inserts", copy=True):
         """How often each distinct (group, member) pair occurs: the spans of `source` ("inserts" or "hits", as in tally()) are the
         members, the held column of tally_hold names the group of their line -- paired, sorted and counted on the device.  The two scans
-        must number lines alike (SEEQDEV_FASTQ in both or in neither, the same buffer).  -> dict: nspans, npaired, nlong, nforeign,
+        must number lines alike (SEEQDEV_FASTQ in both or in neither; the buffers may differ).  -> dict: nspans, npaired, nlong, nforeign,
         nungrouped, npairs, ngroups, max_len, passes; copy adds pairs (TALLY_PAIR_DTYPE, ordered by group, then member: the sparse count
         matrix in row order) and groups (TALLY_GROUP_DTYPE: per group its reads, the rank of its first pair and its distinct members:
         tally_members).  copy=False leaves both on the device (tally_pairs_device_ptr / tally_pairs_table, tally_groups_device_ptr /
@@ -608,6 +608,56 @@ class Scanner:
         cnt = _capi.seeqdev_tally_library_counts_t()
         _check(self._lib.seeqdevScanTallyHoldLibrary(self._h, src, *self._text_args(t), C.byref(cnt)))
         return self._library_counts(cnt)
+
+    # ---- key columns appended to the held column (include/seeq_amd.h: seeqdevScanTallyHoldAppend / seeqdevScanTallyHoldAppendLibrary) ----
+    def tally_hold_append(self, text=None, source="inserts", library=False):
+        """Append a key column to the held column, on the device: the keys of `source` ("inserts", "hits", "gated", "demux" -- built as
+        tally_hold builds them; library=True: assigned to the library as tally_hold_library assigns them, "demux" excluded) are joined
+        to the held records by line, the first record of a line deciding, and every held key becomes (key << width) | new key -- or 0
+        where either is missing.  tally_grouped, tally_collapse and the library then work on the tuples: (cell, guide) x UMI.  text: the
+        tensor of THIS source (as t in tally()), which may be another buffer than the hold's as long as its lines number alike.  -> dict: column (what the
+        corresponding hold returns for the source), nrecords, nbefore, nheld, ndropped, width, key_bits, ncolumns.  The widths sum to at
+        most 63 bits (SeeqDeviceError, E2BIG, the held column unchanged); hold_columns / hold_split take the group words apart."""
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX,
+               "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
+        cnt = _capi.seeqdev_tally_append_counts_t()
+        if library:
+            col = _capi.seeqdev_tally_library_counts_t()
+            _check(self._lib.seeqdevScanTallyHoldAppendLibrary(self._h, src, *self._text_args(text), C.byref(col), C.byref(cnt)))
+            column = self._library_counts(col)
+        else:
+            col = _capi.seeqdev_tally_hold_counts_t()
+            _check(self._lib.seeqdevScanTallyHoldAppend(self._h, src, *self._text_args(text), C.byref(col), C.byref(cnt)))
+            column = {name: int(getattr(col, name)) for name, _ in _capi.seeqdev_tally_hold_counts_t._fields_}
+        res = {name: int(getattr(cnt, name)) for name, _ in _capi.seeqdev_tally_append_counts_t._fields_ if name != "reserved"}
+        res["column"] = column
+        return res
+
+    def hold_columns(self):
+        """The widths in bits of the held key's columns, column 0 (the hold's) first; [] without a held column."""
+        w = (C.c_uint32 * _capi.SEEQDEV_TALLY_COLUMNS)()
+        n = self._lib.seeqdevScanTallyHoldColumns(self._h, w, _capi.SEEQDEV_TALLY_COLUMNS)
+        _check(min(n, 0))
+        return [int(w[c]) for c in range(n)]
+
+    def held_count(self):
+        """Records of the held column (0 without one): the largest `first` seeqdevScanCopyHeld accepts, found on the host."""
+        fits = lambda k: self._lib.seeqdevScanCopyHeld(self._h, None, None, k, 0) == 0      # noqa: E731
+        lo, hi = 0, 1 << 32                                 # fits(lo), not fits(hi)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+        return lo
+
+    def held(self, copy=True):
+        """The held column as it stands: -> dict: nrecords, columns (hold_columns()); copy adds lines (uint32) and keys (uint64, 0: no
+        key), one per held record in record order."""
+        res = dict(nrecords=self.held_count(), columns=self.hold_columns())
+        if copy:
+            n = res["nrecords"]
+            res["lines"], res["keys"] = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+            _check(self._lib.seeqdevScanCopyHeld(self._h, res["lines"].ctypes.data if n else None, res["keys"].ctypes.data if n else None, 0, n))
+        return res
 
     # ---- the base-quality gate in front of the tallies (include/seeq_amd.h: seeqdevScanQualityGate) ----
     def quality_gate(self, t=None, source="inserts", min_qual=20, base=33, max_low=0, reach=1024, copy=True):
@@ -806,6 +856,24 @@ def tally_members(result, group):
         return pairs[:0]
     first = int(groups["first"][at])
     return pairs[first:first + int(groups["ndistinct"][at])]
+
+
+def hold_split(keys, widths):
+    """Group words of a held key of several columns -> a tuple of uint64 arrays, one per column (column 0, the hold's, first): what
+    seeqdevTallySplit does per key, for a whole array -- result["groups"]["group"], result["pairs"]["group"] of a tally_grouped() behind
+    tally_hold_append, with widths = Scanner.hold_columns().  ValueError: no column or more than 8, widths that sum to more than 63 bits,
+    a key with bits above them."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    widths = [int(w) for w in widths]
+    if not 1 <= len(widths) <= _capi.SEEQDEV_TALLY_COLUMNS or any(w < 0 for w in widths) or sum(widths) > 63:
+        raise ValueError("hold_split: 1 .. %d columns whose widths sum to at most 63 bits, not %r" % (_capi.SEEQDEV_TALLY_COLUMNS, widths))
+    if len(keys) and int(keys.max()) >> sum(widths):
+        raise ValueError("hold_split: a key with bits above the %d of its columns" % sum(widths))
+    out, rest = [], keys
+    for w in reversed(widths):
+        out.append(rest & np.uint64((1 << w) - 1))
+        rest = rest >> np.uint64(w)
+    return tuple(reversed(out))
 
 
 # One row of seeqdevScanTallyCollapse's group rows (seeq_amd.h: seeqdev_tally_collapse_t, 16 bytes).
