@@ -338,8 +338,8 @@ int seeqdevScanLastStrandsMs(const seeqdev_scan_t * scan, float * merge_ms);
  * (SQ_STREAM), NULL scan / left / right / counts, NULL text with bytes, max_len != 0 && min_len > max_len, a pattern on another device,
  * SEEQDEV_FASTA together with SEEQDEV_FASTQ.  E2BIG: more than 2^32 - 1 records in either list.
  * ONE orientation per call: for reads off the other strand call again with left = seeqdevPatternRevComp(right) and
- * right = seeqdevPatternRevComp(left).  One-sided cuts (what lies before a right flank alone, after a left flank alone) need line
- * lengths, which the records do not carry: not served.
+ * right = seeqdevPatternRevComp(left).  One-sided cuts (what lies before a right flank alone, after a left flank alone, fixed
+ * columns of a line) need line lengths, which the records do not carry: seeqdevScanAnchor (CUTS AT FIXED OFFSETS below) finds them.
  * seeqdevScanInsertText: the inserts cut out of the text, on the device -- every insert's bytes followed by '\n', in record order (output
  * line k is record k; an empty insert is an empty line), ready for the next stage (a second scan, seeqdevScanRunDemux).  d_text / nbytes:
  * the text the call scanned; d_text == NULL: the context's staged text of the last seeqdevScanHostInserts (EINVAL when another host call
@@ -386,6 +386,7 @@ int seeqdevScanLastInsertsMs(const seeqdev_scan_t * scan, float * join_ms);
  *                        fetched with SEEQDEV_WANT_RECORDS, or of a both-strands call.  A minus-strand hit is tallied as the bytes of
  *                        the text, NOT reverse-complemented.
  *                        SEEQDEV_TALLY_GATED: the records the context's last quality gate passed (THE BASE-QUALITY GATE below).
+ *                        SEEQDEV_TALLY_ANCHORED: the spans the context's last anchor call cut (CUTS AT FIXED OFFSETS below).
  *   key                  of a span of L <= SEEQDEV_TALLY_MAX_LEN bases, every byte one of ACGTUacgtu:
  *                        (1 << 2L) | sum of code(b_i) << 2(L - 1 - i), code = (ASCII >> 1) & 3 as in the packed batches below
  *                        (A 0, C 1, T/U 2, G 3).  The leading 1 carries the length: the empty span has key 1; bit 63 is never set;
@@ -683,7 +684,10 @@ int seeqdevTallySplit(uint64_t key, const uint32_t * widths, int ncolumns, uint6
  * the fourth line of the span's FASTQ record -- and keeps the records whose span passes in arrays of its own, which
  * SEEQDEV_TALLY_GATED names as the source of seeqdevScanTally, seeqdevScanTallyLibrary, seeqdevScanTallyHold,
  * seeqdevScanTallyHoldLibrary and seeqdevScanTallyGrouped: they run unchanged over the gated records.
- *   source               SEEQDEV_TALLY_INSERTS or SEEQDEV_TALLY_HITS, with the preconditions and the NULL-text rule of seeqdevScanTally;
+ *   source               SEEQDEV_TALLY_INSERTS or SEEQDEV_TALLY_HITS, with the preconditions and the NULL-text rule of seeqdevScanTally,
+ *                        or SEEQDEV_TALLY_ANCHORED (CUTS AT FIXED OFFSETS below: a barcode or UMI cut by position is gated before it is
+ *                        counted; the text is the one the anchored records were found in, NULL only where the anchor's own source was the
+ *                        inserts, and a tally over the gated records then keeps that rule);
  *                        anything else (SEEQDEV_TALLY_GATED and SEEQDEV_TALLY_DEMUX included): EINVAL.
  *   the rule             positional, like SEEQDEV_FASTQ: nothing looks for '@' or '+'.  A span is bytes [start, end) of the line at its
  *                        offset `off`.  Its kind, decided in this order:
@@ -727,6 +731,69 @@ int seeqdevScanCopyGated       (seeqdev_scan_t * scan, void * host_out /* 16-byt
 int seeqdevScanCopyGatedOffsets(seeqdev_scan_t * scan, uint64_t * host_out, size_t first, size_t n);
 int seeqdevScanCopyGateKinds   (seeqdev_scan_t * scan, uint8_t * host_out, size_t first, size_t n);   /* one kind per SOURCE record */
 int seeqdevScanLastQualityGateMs(const seeqdev_scan_t * scan, float * ms);
+
+/* CUTS AT FIXED OFFSETS -- most read layouts have no two flanks: a cell barcode in columns 0 .. 16 and a UMI in columns 16 .. 28 of read 1
+ * have none, "the 20 bases in front of the scaffold" and "the 12 bases behind the sample barcode" have one (the reference's Python module
+ * calls them matchPrefix / matchSuffix).  seeqdevScanAnchor REWRITES, ON THE DEVICE, the span of every record of a record array to a cut
+ * measured from the record or from the line's start, finds the line's end where the cut needs it, and keeps the records whose cut fits in
+ * arrays of its own, which SEEQDEV_TALLY_ANCHORED names as the source of seeqdevScanTally, seeqdevScanTallyLibrary, seeqdevScanTallyHold,
+ * seeqdevScanTallyHoldLibrary, seeqdevScanTallyGrouped, seeqdevScanTallyHoldAppend, seeqdevScanTallyHoldAppendLibrary and
+ * seeqdevScanQualityGate: they run unchanged over the anchored records.
+ *   source               SEEQDEV_TALLY_INSERTS or SEEQDEV_TALLY_HITS, with the preconditions and the NULL-text rule of seeqdevScanTally;
+ *                        anything else (SEEQDEV_TALLY_GATED, SEEQDEV_TALLY_DEMUX and SEEQDEV_TALLY_ANCHORED included): EINVAL.
+ *   anchor, skip, len    SEEQDEV_ANCHOR_AFTER: len bytes from `skip` bytes behind the record's end; SEEQDEV_ANCHOR_BEFORE: len bytes that end
+ *                        `skip` bytes in front of the record's start; SEEQDEV_ANCHOR_LINE: columns [skip, skip + len) of the line.
+ *                        len == 0: as far as the line goes -- to its end (AFTER, LINE), from its start (BEFORE).
+ *   the rule             positional.  The source record is (line, start, end, w) with its line offset `off`, n = nbytes, all sums in 64
+ *                        bits.  Its kind:
+ *                          bad     end < start, or off > n, or end > n - off: no byte is loaded, the call fails with EIO (the context
+ *                                  stays usable);
+ *                          BEFORE  skip > start: short.  e = start - skip; s = 0 for len == 0, else short for len > e, else e - len: kept
+ *                                  (s, e).  No text byte is ever loaded in this mode.
+ *                          AFTER / LINE  s = (end for AFTER, 0 for LINE) + skip, e = s + len.  len > 0 and e <= end: kept (s, e) -- the
+ *                                  record vouches for [0, end) of its line, no byte is loaded.  Else p = off + end, lim = min(n, p + reach),
+ *                                  i = the first '\n' in text[p, lim).  No such i and lim < n (the text goes on beyond the reach): kept
+ *                                  (s, e) for len > 0, FAR for len == 0.  No such i and lim == n: L = n - off, the text's end is the
+ *                                  line's end.  Else L = i - off.  len == 0: short for s > L, else e = L (s == L: an empty span, kept);
+ *                                  len > 0: short for e > L.
+ *                          e > 2^32 - 1: short, wherever a span would be kept.
+ *                        A kept record goes out as (line, s, e, w): words 0 and 3 are the source's, untouched -- dist with
+ *                        SEEQDEV_HIT_MINUS, both distances of an insert record --, its 8-byte offset beside it.  Positions are the
+ *                        text's: the strand bit is carried, not interpreted.  A '\r' belongs to the line (the tally calls it foreign).
+ *                        Nothing outside [0, nbytes) is read.
+ *   counts               nspans == nkept + nshort + nfar; span_bytes: the sum of e - s over the kept records.  The check skip + len <=
+ *                        reach guarantees that a call with len > 0 never returns FAR.
+ * EINVAL, before any device call: NULL scan / counts, an unknown source or anchor, NULL text with bytes, reach outside 1 .. 65536,
+ * anchor != SEEQDEV_ANCHOR_BEFORE && len > 0 && skip + len > reach, and seeqdevScanTally's cases for the source.  E2BIG: more than
+ * 2^32 - 1 records.  EIO: a bad record, or an internal inconsistency (the kinds must sum to nspans, the compaction must have placed nkept
+ * records).
+ * Synchronous.  The call reads the source arrays and writes only its own: the record arrays, what there is to fetch, the inserts result,
+ * the gated arrays, the held column, every tally table and the library are afterwards what they were -- so two anchors over the same source
+ * compose: the barcode, then a hold; the UMI, then the grouped tally.  The anchored arrays -- seeqdevScanAnchoredDevice /
+ * seeqdevScanCopyAnchored / seeqdevScanCopyAnchoredOffsets, and seeqdevScanCopyAnchorKinds (one kind per SOURCE record) -- are COPIES: valid
+ * across later scans and inserts calls, until the context's next anchor call or seeqdevScanFree.  An anchor that kept nothing is a result;
+ * without a completed anchor SEEQDEV_TALLY_ANCHORED is EINVAL.  A call over SEEQDEV_TALLY_ANCHORED is given the text the anchored records
+ * were found in; NULL is legal only when the anchor's own source was the inserts: the staged text, as there.
+ * LINES WITHOUT A FLANK: the pattern "N" at distance 0, fetched with records, gives the record (line, 0, 1, 0) for every line whose first
+ * byte is a base (an empty line, or one that starts with another byte, has none); SEEQDEV_ANCHOR_LINE over those records cuts columns
+ * [skip, skip + len) of every read.
+ * Device memory of its own: 5 bytes per source record, 24 bytes per tile of 1 024, 24 bytes per kept record.  (An addition of this
+ * boundary.) */
+#define SEEQDEV_TALLY_ANCHORED 5   /* the spans of the context's last anchor call */
+#define SEEQDEV_ANCHOR_AFTER   0   /* behind the record's end */
+#define SEEQDEV_ANCHOR_BEFORE  1   /* in front of the record's start */
+#define SEEQDEV_ANCHOR_LINE    2   /* from the line's first byte */
+#define SEEQDEV_ANCHOR_KEPT    0   /* the kinds seeqdevScanCopyAnchorKinds serves */
+#define SEEQDEV_ANCHOR_SHORT   1
+#define SEEQDEV_ANCHOR_FAR     2
+typedef struct { uint64_t nspans, nkept, nshort, nfar, span_bytes; } seeqdev_anchor_counts_t;   /* 40 bytes */
+int seeqdevScanAnchor(seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes,
+                      int anchor, uint32_t skip, uint32_t len, uint32_t reach, seeqdev_anchor_counts_t * counts);
+const seeqdev_hit_t * seeqdevScanAnchoredDevice(const seeqdev_scan_t * scan);
+int seeqdevScanCopyAnchored       (seeqdev_scan_t * scan, void * host_out /* 16-byte records */, size_t first, size_t n);
+int seeqdevScanCopyAnchoredOffsets(seeqdev_scan_t * scan, uint64_t * host_out, size_t first, size_t n);
+int seeqdevScanCopyAnchorKinds    (seeqdev_scan_t * scan, uint8_t * host_out, size_t first, size_t n);   /* one kind per SOURCE record */
+int seeqdevScanLastAnchorMs(const seeqdev_scan_t * scan, float * ms);
 
 /* PACKED READ BATCHES -- 2 bits per base instead of a byte: a quarter of the HBM (and PCIe) traffic of the ASCII scan for
  * read sets that are kept packed anyway (BAM, .2bit, a sequencer's own format).  Layout, all device pointers:

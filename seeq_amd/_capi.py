@@ -141,6 +141,15 @@ class seeqdev_qgate_counts_t(C.Structure):
                 ("nmisfit", C.c_uint64), ("low_bases", C.c_uint64)]
 
 
+SEEQDEV_TALLY_ANCHORED = 5          # the spans of the context's last anchor call
+SEEQDEV_ANCHOR_AFTER, SEEQDEV_ANCHOR_BEFORE, SEEQDEV_ANCHOR_LINE = 0, 1, 2
+SEEQDEV_ANCHOR_KEPT, SEEQDEV_ANCHOR_SHORT, SEEQDEV_ANCHOR_FAR = 0, 1, 2
+
+
+class seeqdev_anchor_counts_t(C.Structure):
+    _fields_ = [("nspans", C.c_uint64), ("nkept", C.c_uint64), ("nshort", C.c_uint64), ("nfar", C.c_uint64), ("span_bytes", C.c_uint64)]
+
+
 # Every symbol the three public headers declare (tests check the .so exports all of them).
 EXPORTS = [
     # libseeq.h
@@ -169,6 +178,8 @@ EXPORTS = [
     "seeqdevScanTallyHoldAppend", "seeqdevScanTallyHoldAppendLibrary", "seeqdevScanTallyHoldColumns", "seeqdevScanCopyHeld", "seeqdevTallySplit",
     "seeqdevScanQualityGate", "seeqdevScanGatedDevice", "seeqdevScanCopyGated", "seeqdevScanCopyGatedOffsets", "seeqdevScanCopyGateKinds",
     "seeqdevScanLastQualityGateMs",
+    "seeqdevScanAnchor", "seeqdevScanAnchoredDevice", "seeqdevScanCopyAnchored", "seeqdevScanCopyAnchoredOffsets", "seeqdevScanCopyAnchorKinds",
+    "seeqdevScanLastAnchorMs",
     "seeqdevScanLastRuns", "seeqdevScanFallback", "seeqdevScanLastPlan",
 ]
 
@@ -389,6 +400,15 @@ def lib():
         getattr(L, name).restype = C.c_int
     L.seeqdevScanLastQualityGateMs.argtypes = [C.c_void_p, P(C.c_float)]
     L.seeqdevScanLastQualityGateMs.restype = C.c_int
+    L.seeqdevScanAnchor.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, P(seeqdev_anchor_counts_t)]
+    L.seeqdevScanAnchor.restype = C.c_int
+    L.seeqdevScanAnchoredDevice.argtypes = [C.c_void_p]
+    L.seeqdevScanAnchoredDevice.restype = C.c_void_p
+    for name in ("seeqdevScanCopyAnchored", "seeqdevScanCopyAnchoredOffsets", "seeqdevScanCopyAnchorKinds"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        getattr(L, name).restype = C.c_int
+    L.seeqdevScanLastAnchorMs.argtypes = [C.c_void_p, P(C.c_float)]
+    L.seeqdevScanLastAnchorMs.restype = C.c_int
     L.seeqdevScanPacked.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(seeqdev_packed_t), C.c_int, C.c_int]
     L.seeqdevScanPacked.restype = C.c_int
     L.seeqdevPackReads.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]

@@ -117,6 +117,9 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_tally_library.h"
 #include "seeq_tally_collapse.h"
 #include "seeq_qgate.h"
+#include "seeq_anchor.h"
+static_assert(SEEQ_ANCHOR_AFTER == SEEQDEV_ANCHOR_AFTER && SEEQ_ANCHOR_BEFORE == SEEQDEV_ANCHOR_BEFORE && SEEQ_ANCHOR_LINE == SEEQDEV_ANCHOR_LINE &&
+              SEEQ_ANCHOR_KEPT == SEEQDEV_ANCHOR_KEPT && SEEQ_ANCHOR_SHORT == SEEQDEV_ANCHOR_SHORT && SEEQ_ANCHOR_FAR == SEEQDEV_ANCHOR_FAR, "the anchor's constants");
 static_assert(sizeof(seeqdev_tally_pair_t) == 24 && sizeof(seeqdev_tally_group_t) == 24, "pair and group entries are written as three 64-bit words");
 static_assert(sizeof(seeqdev_tally_collapse_t) == sizeof(uint4) && SEEQ_COLLAPSE_DIRECTIONAL == SEEQDEV_COLLAPSE_DIRECTIONAL && SEEQ_COLLAPSE_ANY == SEEQDEV_COLLAPSE_ANY,
               "collapse rows are written as uint4");
@@ -604,6 +607,15 @@ struct seeqdev_scan {
    bool      qg_done;                                     /* a gate has completed: qg_n records (none included) are a result */
    bool      qg_from_inserts;                             /* ... and its source was the inserts: a NULL text is the staged one */
    EventPair tm_qg;                                       /* profiling: around the gate's launches and counter copies */
+   /* seeqdevScanAnchor (seeq_anchor.h): allocated by the first anchor call.  It reads a source's record arrays and writes these; the kinds
+      and cut ends (an_kind, an_end: an_nsrc source records) and the kept records (an_rec, an_off: an_n) are copies, valid until the next anchor */
+   uint8_t  *an_kind; uint32_t *an_end; uint32_t *an_bsum; size_t cap_an;      /* per source record: its kind, the end of its cut; per tile: the six numbers */
+   uint4    *an_rec; uint64_t *an_off; size_t cap_an_out; /* the kept records, rewritten, and their line offsets */
+   AnchorCnt *d_ancnt, *h_ancnt;                          /* h_ pinned */
+   size_t    an_n, an_nsrc;                               /* kept records; source records of the last anchor */
+   bool      an_done;                                     /* an anchor has completed: an_n records (none included) are a result */
+   bool      an_from_inserts;                             /* ... and its source was the inserts: a NULL text is the staged one */
+   EventPair tm_an;                                       /* profiling: around the anchor's launches and counter copies */
    /* packed read batches (seeqdevScanPacked) */
    uint32_t *pk_cand, *pk_slot, *pk_coff; uint64_t *pk_bmask; size_t cap_pk_reads;      /* candidate columns per read of a segment; per block of 64 reads: candidates before it, their mask */
    uint8_t  *pk_stage; size_t cap_pk_stage;               /* ASCII lines of the candidate reads */
@@ -726,7 +738,7 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
 {
    if (!s) return;
    (void)use_device(s->device);
-   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl, &s->tm_tg, &s->tm_tc, &s->tm_qg})
+   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl, &s->tm_tg, &s->tm_tc, &s->tm_qg, &s->tm_an})
       if (t->made) { (void)hipEventDestroy(t->ev[0]); (void)hipEventDestroy(t->ev[1]); }
    (void)hipStreamSynchronize(s->stream);
    ws_free_all(&s->ws);
@@ -1900,6 +1912,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 #include "seeq_tally_library_host.h"
 #include "seeq_tally_collapse_host.h"
 #include "seeq_qgate_host.h"
+#include "seeq_anchor_host.h"
 
 extern "C" int seeqdevScanLastCopyMs(const seeqdev_scan_t *s, float *h2d_ms)
 {

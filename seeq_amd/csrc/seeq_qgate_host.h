@@ -78,7 +78,7 @@ extern "C" int seeqdevScanQualityGate(seeqdev_scan_t *s, int source, const void 
    const uint64_t *off;
    uint64_t n;
    seeqerr = 0;
-   if ((source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS) || (uint64_t)base + min_qual > 255u || reach < 1u || reach > SEEQ_QGATE_REACH_MAX) {
+   if ((source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS && source != SEEQDEV_TALLY_ANCHORED) || (uint64_t)base + min_qual > 255u || reach < 1u || reach > SEEQ_QGATE_REACH_MAX) {
       errno = EINVAL;
       return -1;
    }
@@ -89,7 +89,7 @@ extern "C" int seeqdevScanQualityGate(seeqdev_scan_t *s, int source, const void 
    if (qgate_run(s, rec, off, (uint32_t)n, d_text, nbytes, base + min_qual, max_low, reach, counts)) return -1;
    s->qg_n = (size_t)counts->npassed;
    s->qg_nsrc = (size_t)n;
-   s->qg_from_inserts = source == SEEQDEV_TALLY_INSERTS;
+   s->qg_from_inserts = source == SEEQDEV_TALLY_INSERTS || (source == SEEQDEV_TALLY_ANCHORED && s->an_from_inserts);      /* (cut from inserts: still theirs) */
    s->qg_done = true;                                      /* (a gate that passed nothing included) */
    return 0;
 }

@@ -160,8 +160,9 @@ static int tally_run(seeqdev_scan *s, const uint4 *rec, const uint64_t *off, uin
    return 0;
 }
 
-/* Which record array a source names: SEEQDEV_TALLY_INSERTS, SEEQDEV_TALLY_HITS or SEEQDEV_TALLY_GATED (the spans the last quality gate
-   passed: seeq_qgate_host.h), with the preconditions of each (EINVAL; the staged text for a NULL text of the inserts). */
+/* Which record array a source names: SEEQDEV_TALLY_INSERTS, SEEQDEV_TALLY_HITS, SEEQDEV_TALLY_GATED (the spans the last quality gate
+   passed: seeq_qgate_host.h) or SEEQDEV_TALLY_ANCHORED (the spans the last anchor call cut: seeq_anchor_host.h), with the preconditions
+   of each (EINVAL; the staged text for a NULL text of the inserts). */
 static int tally_source(seeqdev_scan *s, int source, const void **d_text, size_t *nbytes, const uint4 **rec, const uint64_t **off, uint64_t *n)
 {
    if (source == SEEQDEV_TALLY_INSERTS) {
@@ -182,6 +183,15 @@ static int tally_source(seeqdev_scan *s, int source, const void **d_text, size_t
       }
       if (staged_text(s, "tally", d_text, nbytes)) return -1;
       *rec = s->qg_rec; *off = s->qg_off; *n = s->qg_n;
+   } else if (source == SEEQDEV_TALLY_ANCHORED) {
+      /* what seeqdevScanAnchoredDevice serves: the anchor's own copies, under the gated records' text rule */
+      if (!s->an_done || (!*d_text && !s->an_from_inserts)) {
+         snprintf(g_last_error, sizeof g_last_error, "tally: %s", !s->an_done ? "the context holds no result of an anchor call" : "the anchored hits need the text they were found in");
+         errno = EINVAL;
+         return -1;
+      }
+      if (staged_text(s, "tally", d_text, nbytes)) return -1;
+      *rec = s->an_rec; *off = s->an_off; *n = s->an_n;
    } else {
       /* what seeqdevScanCopyRecords serves: the records of a fetched scan or of a both-strands call.  A context with nothing to fetch
          (fresh, or after a multi, demux or inserts call: scan_forget) has none; a packed scan's offsets are no offsets into a text */
@@ -205,7 +215,7 @@ static int tally_enter(seeqdev_scan *s, const void *counts, int source, const ch
                        const uint64_t **off, uint64_t *n)
 {
    seeqerr = 0;
-   if (!s || !counts || (source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS && source != SEEQDEV_TALLY_GATED) || (!*d_text && *nbytes)) { errno = EINVAL; return -1; }
+   if (!s || !counts || (source != SEEQDEV_TALLY_INSERTS && source != SEEQDEV_TALLY_HITS && source != SEEQDEV_TALLY_GATED && source != SEEQDEV_TALLY_ANCHORED) || (!*d_text && *nbytes)) { errno = EINVAL; return -1; }
    if (missing) {
       snprintf(g_last_error, sizeof g_last_error, "%s", missing);
       errno = EINVAL;

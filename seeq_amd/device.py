@@ -184,6 +184,12 @@ class RevCompPattern:
 PLAN_FIELDS = ("rc", "path", "fw", "use_stream", "use_pair", "use_myers", "filter", "stream_ll", "stream_sub", "stream_wu", "verify", "order2",
                "leaders", "window_ok", "ll_filter", "skip_back")
 
+# the names of the record arrays the tally entries take as `source` (seeq_amd.h); the holds and the append take a demultiplex too
+_SPAN_SOURCES = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "gated": _capi.SEEQDEV_TALLY_GATED,
+                 "anchored": _capi.SEEQDEV_TALLY_ANCHORED}
+_HOLD_SOURCES = dict(_SPAN_SOURCES, demux=_capi.SEEQDEV_TALLY_DEMUX)
+_ANCHORS = {"after": _capi.SEEQDEV_ANCHOR_AFTER, "before": _capi.SEEQDEV_ANCHOR_BEFORE, "line": _capi.SEEQDEV_ANCHOR_LINE}
+
 
 class Scanner:
     def __init__(self, stream=None):
@@ -430,7 +436,7 @@ class Scanner:
         staged.  -> dict: nspans, ntallied, nlong, nforeign, ndistinct, max_len, passes; copy adds keys and counts, uint64 arrays in
         ascending key order (by length, then A < C < T < G): tally_key / tally_decode / tally_lookup.  copy=False leaves the table on
         the device (tally_device_ptr / tally_table)."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
+        src = _SPAN_SOURCES.get(source, source)
         cnt = _capi.seeqdev_tally_counts_t()
         _check(self._lib.seeqdevScanTally(self._h, src, C.c_void_p(t.data_ptr()) if t is not None else None, t.numel() if t is not None else 0, C.byref(cnt)))
         res = dict(nspans=int(cnt.nspans), ntallied=int(cnt.ntallied), nlong=int(cnt.nlong), nforeign=int(cnt.nforeign), ndistinct=int(cnt.ndistinct),
@@ -468,8 +474,7 @@ class Scanner:
         winning pattern + 1 of the last demultiplex ("demux"; t is not needed; an ambiguous line is held without a key).  t: as in
         tally().  -> dict: nspans, nheld, nlong, nforeign, nambiguous, max_len, key_bits.  The column survives scans, inserts calls,
         demultiplexes and plain tallies; the next tally_hold replaces it."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX,
-               "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
+        src = _HOLD_SOURCES.get(source, source)
         cnt = _capi.seeqdev_tally_hold_counts_t()
         _check(self._lib.seeqdevScanTallyHold(self._h, src, *self._text_args(t), C.byref(cnt)))
         return dict(nspans=int(cnt.nspans), nheld=int(cnt.nheld), nlong=int(cnt.nlong), nforeign=int(cnt.nforeign), nambiguous=int(cnt.nambiguous),
@@ -483,7 +488,7 @@ class Scanner:
         matrix in row order) and groups (TALLY_GROUP_DTYPE: per group its reads, the rank of its first pair and its distinct members:
         tally_members).  copy=False leaves both on the device (tally_pairs_device_ptr / tally_pairs_table, tally_groups_device_ptr /
         tally_groups_table)."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
+        src = _SPAN_SOURCES.get(source, source)
         cnt = _capi.seeqdev_tally_grouped_counts_t()
         _check(self._lib.seeqdevScanTallyGrouped(self._h, src, *self._text_args(t), C.byref(cnt)))
         res = dict(nspans=int(cnt.nspans), npaired=int(cnt.npaired), nlong=int(cnt.nlong), nforeign=int(cnt.nforeign), nungrouped=int(cnt.nungrouped),
@@ -589,7 +594,7 @@ class Scanner:
         nambiguous, nunknown, nlong, nforeign, ndistinct, key_bits, passes; copy adds ids and counts, uint64 arrays in ascending id
         order, entries without a read absent (library_counts makes the dense vector).  The table is the Scanner's tally table
         (tally_device_ptr / tally_table, `key` = id), replaced by the next tally of either kind."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
+        src = _SPAN_SOURCES.get(source, source)
         cnt = _capi.seeqdev_tally_library_counts_t()
         _check(self._lib.seeqdevScanTallyLibrary(self._h, src, *self._text_args(t), C.byref(cnt)))
         res = self._library_counts(cnt)
@@ -603,23 +608,21 @@ class Scanner:
         """tally_hold ("inserts" or "hits") with the held keys assigned to the library: the group of a line is its entry's id, or none.
         A following tally_grouped has one group per library entry seen, erroneous copies folded into their entry.  -> the dict of
         tally_library (ndistinct and passes 0)."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX,
-               "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
+        src = _HOLD_SOURCES.get(source, source)
         cnt = _capi.seeqdev_tally_library_counts_t()
         _check(self._lib.seeqdevScanTallyHoldLibrary(self._h, src, *self._text_args(t), C.byref(cnt)))
         return self._library_counts(cnt)
 
     # ---- key columns appended to the held column (include/seeq_amd.h: seeqdevScanTallyHoldAppend / seeqdevScanTallyHoldAppendLibrary) ----
     def tally_hold_append(self, text=None, source="inserts", library=False):
-        """Append a key column to the held column, on the device: the keys of `source` ("inserts", "hits", "gated", "demux" -- built as
+        """Append a key column to the held column, on the device: the keys of `source` ("inserts", "hits", "gated", "anchored", "demux" -- built as
         tally_hold builds them; library=True: assigned to the library as tally_hold_library assigns them, "demux" excluded) are joined
         to the held records by line, the first record of a line deciding, and every held key becomes (key << width) | new key -- or 0
         where either is missing.  tally_grouped, tally_collapse and the library then work on the tuples: (cell, guide) x UMI.  text: the
         tensor of THIS source (as t in tally()), which may be another buffer than the hold's as long as its lines number alike.  -> dict: column (what the
         corresponding hold returns for the source), nrecords, nbefore, nheld, ndropped, width, key_bits, ncolumns.  The widths sum to at
         most 63 bits (SeeqDeviceError, E2BIG, the held column unchanged); hold_columns / hold_split take the group words apart."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "demux": _capi.SEEQDEV_TALLY_DEMUX,
-               "gated": _capi.SEEQDEV_TALLY_GATED}.get(source, source)
+        src = _HOLD_SOURCES.get(source, source)
         cnt = _capi.seeqdev_tally_append_counts_t()
         if library:
             col = _capi.seeqdev_tally_library_counts_t()
@@ -661,13 +664,13 @@ class Scanner:
 
     # ---- the base-quality gate in front of the tallies (include/seeq_amd.h: seeqdevScanQualityGate) ----
     def quality_gate(self, t=None, source="inserts", min_qual=20, base=33, max_low=0, reach=1024, copy=True):
-        """Keep the spans of `source` ("inserts" or "hits", t as in tally()) whose FASTQ quality bytes are good enough: a span passes when
+        """Keep the spans of `source` ("inserts", "hits" or "anchored", t as in tally()) whose FASTQ quality bytes are good enough: a span passes when
         at most max_low of the quality bytes under it -- in the line two below its own, found within `reach` bytes behind the span --
         are below base + min_qual.  Decided and compacted on the device; the tallies then take source="gated".  -> dict: nspans,
         npassed, nlow, nlong, nfar, nmisfit, low_bases; copy adds records ([npassed, 4] uint32: the source's 16-byte records unchanged,
         in order), offsets (uint64) and kinds (uint8 per SOURCE record: GATE_PASS, GATE_LOW, GATE_LONG, GATE_FAR, GATE_MISFIT).  The
         gated arrays are copies: they survive later scans and inserts calls, until the next quality_gate."""
-        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS}.get(source, source)
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS, "anchored": _capi.SEEQDEV_TALLY_ANCHORED}.get(source, source)
         cnt = _capi.seeqdev_qgate_counts_t()
         _check(self._lib.seeqdevScanQualityGate(self._h, src, *self._text_args(t), min_qual, base, max_low, reach, C.byref(cnt)))
         res = {name: int(getattr(cnt, name)) for name, _ in _capi.seeqdev_qgate_counts_t._fields_}
@@ -705,6 +708,56 @@ class Scanner:
         """Device time of the last quality gate (its launches and counter copies; profiling on), 0 when not measured."""
         ms = C.c_float(0)
         _check(self._lib.seeqdevScanLastQualityGateMs(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    # ---- cuts at fixed offsets from a hit or the line's start (include/seeq_amd.h: seeqdevScanAnchor) ----
+    def anchor(self, text=None, source="hits", anchor="after", skip=0, length=0, reach=1024, copy=True):
+        """Rewrite the span of every record of `source` ("hits" or "inserts"; text: as t in tally()) to a cut at fixed offsets, on the device:
+        anchor "after": `length` bytes from `skip` bytes behind the record's end; "before": `length` bytes that end `skip` bytes in front
+        of its start; "line": columns [skip, skip + length) of its line.  length 0: as far as the line goes (its end is searched within
+        `reach` bytes behind the record's end).  The records whose cut fits are kept in arrays of the anchor's own; the tallies and the
+        quality gate then take source="anchored".  -> dict: nspans, nkept, nshort, nfar, span_bytes; copy adds records ([nkept, 4]
+        uint32: line, the cut's start and end, the source's fourth word), offsets (uint64) and kinds (uint8 per SOURCE record:
+        ANCHOR_KEPT, ANCHOR_SHORT, ANCHOR_FAR).  The anchored arrays are copies: they survive later scans and inserts calls, until the
+        next anchor; the source is untouched, so a second anchor over it sees what the first one saw."""
+        src = {"inserts": _capi.SEEQDEV_TALLY_INSERTS, "hits": _capi.SEEQDEV_TALLY_HITS}.get(source, source)
+        cnt = _capi.seeqdev_anchor_counts_t()
+        _check(self._lib.seeqdevScanAnchor(self._h, src, *self._text_args(text), _ANCHORS.get(anchor, anchor), skip, length, reach, C.byref(cnt)))
+        res = {name: int(getattr(cnt, name)) for name, _ in _capi.seeqdev_anchor_counts_t._fields_}
+        if copy:
+            res["records"] = self.anchored_records(res["nkept"])
+            res["offsets"] = self.anchored_offsets(res["nkept"])
+            res["kinds"] = self.anchor_kinds(res["nspans"])
+        return res
+
+    def anchored_records(self, n, first=0):
+        """Copy records [first, first + n) the last anchor kept to the host -> ndarray [n, 4] u32: line, the cut [start, end), and the
+        source's fourth word (hits: dist with its strand bit; inserts: view as INSERT_DTYPE)."""
+        out = np.zeros((n, 4), dtype=np.uint32)
+        _check(self._lib.seeqdevScanCopyAnchored(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def anchored_offsets(self, n, first=0):
+        """Per anchored record: byte offset of its line in the scanned buffer -> ndarray [n] u64."""
+        out = np.zeros(n, dtype=np.uint64)
+        _check(self._lib.seeqdevScanCopyAnchoredOffsets(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def anchor_kinds(self, n, first=0):
+        """Per record of the last anchor's SOURCE: what its cut was -> ndarray [n] u8."""
+        out = np.zeros(n, dtype=np.uint8)
+        _check(self._lib.seeqdevScanCopyAnchorKinds(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def anchored_device_ptr(self):
+        """Device address of the records the last anchor kept (16 bytes each; valid until this Scanner's next anchor); None when it
+        kept none."""
+        return self._lib.seeqdevScanAnchoredDevice(self._h)
+
+    def last_anchor_ms(self):
+        """Device time of the last anchor (its launches and counter copies; profiling on), 0 when not measured."""
+        ms = C.c_float(0)
+        _check(self._lib.seeqdevScanLastAnchorMs(self._h, C.byref(ms)))
         return float(ms.value)
 
     # ---- several patterns, one text (include/seeq_amd.h: seeqdevScanRunMulti / seeqdevScanHostMulti) ----
@@ -797,6 +850,8 @@ TALLY_DTYPE = np.dtype([("key", "<u8"), ("count", "<u8")])
 # what Scanner.quality_gate's `kinds` hold, per source record
 GATE_PASS, GATE_LOW, GATE_LONG, GATE_FAR, GATE_MISFIT = (_capi.SEEQDEV_QGATE_PASS, _capi.SEEQDEV_QGATE_LOW, _capi.SEEQDEV_QGATE_LONG,
                                                          _capi.SEEQDEV_QGATE_FAR, _capi.SEEQDEV_QGATE_MISFIT)
+# what Scanner.anchor's `kinds` hold, per source record
+ANCHOR_KEPT, ANCHOR_SHORT, ANCHOR_FAR = _capi.SEEQDEV_ANCHOR_KEPT, _capi.SEEQDEV_ANCHOR_SHORT, _capi.SEEQDEV_ANCHOR_FAR
 
 
 def tally_key(seq):
