@@ -576,7 +576,7 @@ int seeqdevScanCopyTallyCollapse(seeqdev_scan_t * scan, seeqdev_tally_collapse_t
  * on; 0 otherwise, and when there was no pair). */
 int seeqdevScanLastTallyCollapseMs(const seeqdev_scan_t * scan, float * ms);
 
-/* COUNTING AGAINST A KNOWN LIBRARY: EXACT OR ONE MISMATCH.  The sequences of a screen or a barcode run are known in advance -- a guide
+/* COUNTING AGAINST A KNOWN LIBRARY: EXACT, ONE MISMATCH, OR ONE EDIT.  The sequences of a screen or a barcode run are known in advance -- a guide
  * library, a whitelist -- and what is asked for is one count per library ENTRY, a read with one sequencing error counted for the entry it
  * came from.  seeqdevScanTally counts distinct OBSERVED sequences: every erroneous copy is a row of its own.  With a library set on the
  * context, a span's key is replaced ON THE DEVICE (seeq_tally_library.h) by its entry's id before the tally's sort, which then runs
@@ -594,6 +594,26 @@ int seeqdevScanLastTallyCollapseMs(const seeqdev_scan_t * scan, float * ms);
  *                            |H| >= 2 -> 0, AMBIGUOUS; |H| == 0 -> 0, UNKNOWN.  Else, under max_mismatch 0 -> 0, UNKNOWN.  Long and
  *                            foreign spans are decided first, exactly as in seeqdevScanTally; the library never sees them.
  *                            nspans = nexact + ncorrected + nambiguous + nunknown + nlong + nforeign; nassigned = nexact + ncorrected.
+ *   seeqdevScanSetLibraryMode  the same call with a MODE in place of max_mismatch: SEEQDEV_LIBRARY_EXACT (0) and SEEQDEV_LIBRARY_SUBST (1) are
+ *                            max_mismatch 0 and 1, exactly; SEEQDEV_LIBRARY_EDIT (2) is ONE EDIT -- a substitution, an insertion or a deletion
+ *                            (Levenshtein distance 1).  Validation, errors, lifetime and "a failed call leaves none" are
+ *                            seeqdevScanSetLibrary's; a mode outside {0, 1, 2} is EINVAL before anything is read.  seeqdevScanSetLibrary
+ *                            itself keeps refusing a max_mismatch other than 0 and 1.
+ *   neighbours under SEEQDEV_LIBRARY_EDIT  of a key k of length L, in three classes that are disjoint because their lengths differ:
+ *                            the 3 L substitutions above; the DELETIONS, length L - 1 (the read carries one base too many): base p of k
+ *                            removed, taken once per run of equal bases (p == 0 or base[p] != base[p - 1]); the INSERTIONS, length L + 1
+ *                            (the read lost a base): base c put in front of position p, 0 <= p <= L, taken where p == 0 or
+ *                            c != base[p - 1] -- 3 L + 4 of them, and only for L <= 30.  The conditions make the neighbours of a class
+ *                            pairwise distinct keys (AAAA finds the entry AAA once, not four times); the three classes together are
+ *                            exactly the sequences at Levenshtein distance 1.  The assignment is the one above with H taken over all
+ *                            three classes: an entry one substitution away and another one deletion away are two, AMBIGUOUS.  A corrected
+ *                            span is SUBSTITUTED, INSERTED or DELETED by the class of the neighbour that was the entry: ncorrected =
+ *                            nsubstituted + ninserted + ndeleted.  A 31-base entry whose read GAINED a base is a span of 32 bytes: LONG,
+ *                            decided before the library sees it, and stays lost.
+ *   seeqdevScanLastLibraryEdits  that split for the context's last completed assignment, of any of the three library entries
+ *                            (seeqdevScanTallyLibrary, seeqdevScanTallyHoldLibrary, seeqdevScanTallyHoldAppendLibrary); all zero after a
+ *                            set call, after a failed call and before any assignment; ninserted = ndeleted = 0 under modes 0 and 1.
+ *                            EINVAL for a NULL argument.
  *   seeqdevScanTallyLibrary  sources, preconditions, staged text, EINVAL / EIO / E2BIG cases: seeqdevScanTally's, unchanged; EINVAL
  *                            without a library, before any device call.  THE TABLE is the context's tally table -- one seeqdev_tally_t
  *                            {key = id, count} per id that occurs, ids ascending, the counts summing to nassigned, entries without a read
@@ -603,14 +623,15 @@ int seeqdevScanLastTallyCollapseMs(const seeqdev_scan_t * scan, float * ms);
  *                            (SEEQDEV_TALLY_DEMUX: EINVAL), then assigns it: the held key of a record is its entry's id, or 0.
  *                            key_bits = bitlen(N); ndistinct and passes are 0.  A following seeqdevScanTallyGrouped runs unchanged: its
  *                            group table has one row per library entry seen, erroneous guides folded into their entry.
- * Synchronous.  Device memory of its own: 12 bytes per library entry (key, id), 8 bytes per tile of 1 024 spans and 16 per 64 misses;
+ * Synchronous.  Device memory of its own: 12 bytes per library entry (key, id), 8 bytes per tile of 1 024 spans and 16 per 64 misses (24
+ * under SEEQDEV_LIBRARY_EDIT);
  * the miss indices (4 bytes per miss) lie in the tally's second key array, which the sort has not touched yet (the hold call allocates
  * the plain tally's key scratch for them).  (The reference counts nothing: an addition of this boundary.) */
 typedef struct {
    uint64_t nspans;      /* records of the source */
    uint64_t nassigned;   /* nexact + ncorrected: the sum of the table's counts */
    uint64_t nexact;      /* spans whose key is a library entry */
-   uint64_t ncorrected;  /* spans one substitution away from exactly one entry */
+   uint64_t ncorrected;  /* spans one substitution (SEEQDEV_LIBRARY_EDIT: one edit) away from exactly one entry */
    uint64_t nambiguous;  /* ... from two or more */
    uint64_t nunknown;    /* spans with a key that is neither */
    uint64_t nlong;       /* spans of more than SEEQDEV_TALLY_MAX_LEN bytes */
@@ -620,7 +641,20 @@ typedef struct {
    uint32_t passes;      /* passes of the sort: ceil(key_bits / 8); 0: nothing was assigned (the hold: 0) */
 } seeqdev_tally_library_counts_t;   /* 80 bytes */
 
+#define SEEQDEV_LIBRARY_EXACT 0
+#define SEEQDEV_LIBRARY_SUBST 1
+#define SEEQDEV_LIBRARY_EDIT  2
+
+typedef struct {
+   uint64_t nsubstituted;   /* corrected spans whose entry has their length */
+   uint64_t ninserted;      /* ... is one base longer: the read lost a base */
+   uint64_t ndeleted;       /* ... is one base shorter: the read carries one base too many */
+   uint64_t reserved;       /* 0 */
+} seeqdev_tally_library_edits_t;   /* 32 bytes */
+
 int seeqdevScanSetLibrary(seeqdev_scan_t * scan, const uint64_t * keys, size_t n, int max_mismatch);
+int seeqdevScanSetLibraryMode(seeqdev_scan_t * scan, const uint64_t * keys, size_t n, int mode);
+int seeqdevScanLastLibraryEdits(const seeqdev_scan_t * scan, seeqdev_tally_library_edits_t * out);
 int seeqdevScanTallyLibrary    (seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_library_counts_t * counts);
 int seeqdevScanTallyHoldLibrary(seeqdev_scan_t * scan, int source, const void * d_text, size_t nbytes, seeqdev_tally_library_counts_t * counts);
 

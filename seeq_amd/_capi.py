@@ -126,6 +126,13 @@ class seeqdev_tally_library_counts_t(C.Structure):
                 ("passes", C.c_uint32)]
 
 
+SEEQDEV_LIBRARY_EXACT, SEEQDEV_LIBRARY_SUBST, SEEQDEV_LIBRARY_EDIT = 0, 1, 2
+
+
+class seeqdev_tally_library_edits_t(C.Structure):
+    _fields_ = [("nsubstituted", C.c_uint64), ("ninserted", C.c_uint64), ("ndeleted", C.c_uint64), ("reserved", C.c_uint64)]
+
+
 class seeqdev_tally_append_counts_t(C.Structure):
     _fields_ = [("nrecords", C.c_uint64), ("nbefore", C.c_uint64), ("nheld", C.c_uint64), ("ndropped", C.c_uint64), ("width", C.c_uint32),
                 ("key_bits", C.c_uint32), ("ncolumns", C.c_uint32), ("reserved", C.c_uint32)]
@@ -174,7 +181,7 @@ EXPORTS = [
     "seeqdevScanCopyTallyGroups", "seeqdevScanLastTallyGroupedMs",
     "seeqdevScanTallyCollapse", "seeqdevScanTallyParentsDevice", "seeqdevScanTallyCollapseDevice", "seeqdevScanCopyTallyParents",
     "seeqdevScanCopyTallyCollapse", "seeqdevScanLastTallyCollapseMs",
-    "seeqdevScanSetLibrary", "seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary",
+    "seeqdevScanSetLibrary", "seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary", "seeqdevScanSetLibraryMode", "seeqdevScanLastLibraryEdits",
     "seeqdevScanTallyHoldAppend", "seeqdevScanTallyHoldAppendLibrary", "seeqdevScanTallyHoldColumns", "seeqdevScanCopyHeld", "seeqdevTallySplit",
     "seeqdevScanQualityGate", "seeqdevScanGatedDevice", "seeqdevScanCopyGated", "seeqdevScanCopyGatedOffsets", "seeqdevScanCopyGateKinds",
     "seeqdevScanLastQualityGateMs",
@@ -378,6 +385,10 @@ def lib():
     L.seeqdevScanLastTallyCollapseMs.restype = C.c_int
     L.seeqdevScanSetLibrary.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     L.seeqdevScanSetLibrary.restype = C.c_int
+    L.seeqdevScanSetLibraryMode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    L.seeqdevScanSetLibraryMode.restype = C.c_int
+    L.seeqdevScanLastLibraryEdits.argtypes = [C.c_void_p, P(seeqdev_tally_library_edits_t)]
+    L.seeqdevScanLastLibraryEdits.restype = C.c_int
     for name in ("seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary"):
         getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(seeqdev_tally_library_counts_t)]
         getattr(L, name).restype = C.c_int

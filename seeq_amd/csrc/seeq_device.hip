@@ -586,8 +586,11 @@ struct seeqdev_scan {
    uint64_t *lb_key; uint32_t *lb_id; size_t cap_lb;      /* per entry: key, id */
    size_t    lb_n;                                        /* entries of the library; 0: the context holds none */
    int       lb_mismatch;                                 /* its max_mismatch: 0 or 1 */
+   int       lb_mode;                                     /* its mode, SEEQDEV_LIBRARY_*: max_mismatch, or 2 -- one edit, indels included */
    uint32_t *lb_sum; size_t cap_lb_sum;                   /* per tile of spans: misses, exact */
    uint4    *lb_nstat; size_t cap_lb_near;                /* per workgroup of the near pass: corrected, ambiguous, unknown, bad */
+   uint2    *lb_nedit; size_t cap_lb_edit;                /* per workgroup of the near pass in the edit mode: inserted, deleted */
+   seeqdev_tally_library_edits_t lb_edits;                /* the split of ncorrected of the last completed assignment; zero: none since the set call */
    TallyLibCnt *d_lbcnt, *h_lbcnt;                        /* h_ pinned */
    /* seeqdevScanTallyCollapse (seeq_tally_collapse.h): reads the two tables of the last grouped call, writes arrays of its own; its result
       (tc_parent: tc_np entries, tc_groups: tc_ng rows) is valid until the next grouped call or the next collapse */

@@ -107,6 +107,7 @@ extern "C" int seeqdevScanTallyHoldAppendLibrary(seeqdev_scan_t *s, int source, 
    uint64_t n;
    if (!counts) { seeqerr = 0; errno = EINVAL; return -1; }
    if (tally_enter(s, column, source, tally_append_missing(s, true), &d_text, &nbytes, &rec, &off, &n)) return -1;
+   memset(&s->lb_edits, 0, sizeof s->lb_edits);             /* (no span with a key: no assignment, and no split of one before) */
    memset(counts, 0, sizeof *counts);
    seeqdev_tally_hold_counts_t held;
    if (tally_hold_run(s, rec, off, (uint32_t)n, false, d_text, nbytes, &held, tally_append_target(s))) return -1;

@@ -1,24 +1,40 @@
 /*
  * seeq_tally_library.h -- counting spans against a KNOWN library: a guide library of a screen, a barcode whitelist.  A span's tally key
- * (seeq_tally.h) is replaced, on the device, by the number of the library entry it is -- exactly, or with one substitution -- and the
- * tally's own sort, run-length pass and table then count entry numbers instead of observed sequences: one row per library entry seen,
- * a read with one sequencing error counted for the entry it came from, and ceil(bitlen(N) / 8) passes of the sort instead of
- * ceil((2 * max_len + 1) / 8).
+ * (seeq_tally.h) is replaced, on the device, by the number of the library entry it is -- exactly, with one substitution, or (the edit
+ * mode) with one substitution, insertion or deletion -- and the tally's own sort, run-length pass and table then count entry numbers
+ * instead of observed sequences: one row per library entry seen, a read with one sequencing error counted for the entry it came from,
+ * and ceil(bitlen(N) / 8) passes of the sort instead of ceil((2 * max_len + 1) / 8).
  *
- * The rule -- plain C++ below, shared with the host driver (tests/tally_library_host_driver.cpp compiles this header with g++):
+ * The rule -- plain C++ below, shared with the host drivers (tests/tally_library_host_driver.cpp and tests/tally_library_edit_host_driver.cpp
+ * compile this header with g++):
  *
  *   library      N >= 1 tally keys in the caller's order, each a valid key (tally_key_len >= 0), pairwise distinct, lengths mixed
  *                freely; N <= SEEQ_TLIB_MAX = 2^24 - 1.  THE ID of entry i is i + 1; id 0 is "no entry".  On the device: the keys
  *                ascending with the ids beside them (tally_lib_prepare sorts and validates on the host).
  *   neighbour    of a key k of length L at position 0 <= p < L with s in {1, 2, 3}: k ^ (s << 2(L - 1 - p)), the three other bases
  *                there (tally_neighbour).  It has k's length; a key has 3 L of them, the empty key none.  Substitutions only: an
- *                insertion or deletion changes the length and makes no neighbour.
+ *                insertion or deletion changes the length and makes no neighbour -- but under the edit mode, below.
  *   assignment   of a span's key k under max_mismatch 0 or 1 (tally_lib_assign):
  *                  k is in the library                          -> its id, EXACT (whatever neighbours of k are in it too);
  *                  else, max_mismatch 1, H = the library entries that are neighbours of k:
  *                     |H| == 1 -> that entry's id, CORRECTED;   |H| >= 2 -> 0, AMBIGUOUS;   |H| == 0 -> 0, UNKNOWN;
  *                  else, max_mismatch 0                         -> 0, UNKNOWN.
- *   long, foreign, bad spans are decided first and exactly as in the plain tally (key 0): the library never sees them.
+ *   edit mode    (SEEQ_TLIB_MODE_EDIT; tally_lib_assign_mode) three classes of neighbour, disjoint because their lengths differ:
+ *                  substitution  as above, length L, 3 L of them;
+ *                  deletion      (the read carries one base too many) base p of k removed, length L - 1 (tally_del_neighbour), taken only at
+ *                                the canonical positions p == 0 || base[p] != base[p - 1], one per run of equal bases; L == 0 has none,
+ *                                L == 1 gives the empty key;
+ *                  insertion     (the read lost a base) base c put in front of position p, 0 <= p <= L, length L + 1
+ *                                (tally_ins_neighbour), taken only where p == 0 || c != base[p - 1] -- 3 L + 4 of them -- and only for
+ *                                L <= 30: a key of 32 bases does not exist.
+ *                The canonical conditions make the neighbours of one class pairwise distinct keys, so "entries found" is a sum as in the
+ *                substitution pass (without them AAAA finds the entry AAA four times and is called ambiguous); the union of the three
+ *                classes is exactly the keys at Levenshtein distance 1.  Exact wins; else H = the entries among all neighbours of the
+ *                three classes: |H| == 1 -> that id, CORRECTED -- substituted, inserted or deleted by the class it came from
+ *                (SEEQ_TLIB_BY_*); |H| >= 2 -> 0, AMBIGUOUS (an entry one substitution away and another one deletion away are two);
+ *                |H| == 0 -> 0, UNKNOWN.  ncorrected = nsubstituted + ninserted + ndeleted.
+ *   long, foreign, bad spans are decided first and exactly as in the plain tally (key 0): the library never sees them.  A 31-base entry
+ *                whose read GAINED a base is a span of 32 bytes: long, and it stays lost under every mode.
  *   counts       nspans = nexact + ncorrected + nambiguous + nunknown + nlong + nforeign;  nassigned = nexact + ncorrected.
  *   table        one {key = id, count} per id that occurs, ids ascending; the counts sum to nassigned.
  *   passes       of the sort over ids: ceil(bitlen(N) / 8) when anything was assigned, else 0 (tally_lib_passes).
@@ -44,7 +60,13 @@
  *                          L) owns one miss, lane p < L searches the three neighbours at position p (stepped together), the half sums
  *                          (neighbours found, ids found) with __shfl_xor at distances 16 .. 1, and its lane 0 stores the id when exactly
  *                          one was found, else 0.  Per workgroup {corrected, ambiguous, unknown, bad}.
- *   k_tally_near_top       one workgroup: their totals (of a workgroup per 8 misses it took 0.12 ms for 0.9 M misses: hence the rounds).
+ *   k_tally_assign_near_edit  the same pass in its second instance (one template, tally_assign_near<EDIT>), for the edit mode, with the
+ *                          same geometry: lane p owns its three substitutions (p < L), the deletion at p (p < L, canonical) and the
+ *                          insertions in front of p (p <= L <= 30: four for lane 0, three for the others); its at most eight searches are
+ *                          stepped together, eight independent loads in flight.  The half sums (entries found, ids found, the class of
+ *                          what was found) in two words; per workgroup two more counts, {inserted, deleted} of the corrected.
+ *   k_tally_near_top       one workgroup: their totals, the edit instance's two counts too (of a workgroup per 8 misses it took 0.12 ms
+ *                          for 0.9 M misses: hence the rounds).
  *
  * Compacting first makes the near pass's work proportional to misses x L: one thread per span doing all 3 L searches would leave a
  * 64-lane wave walking 3 L dependent searches for the few lanes that missed.
@@ -71,12 +93,45 @@
 #define SEEQ_TLIB_AMBIGUOUS 2
 #define SEEQ_TLIB_UNKNOWN   3
 
+#define SEEQ_TLIB_MODE_EXACT 0                              /* the library's mode = SEEQDEV_LIBRARY_* (seeq_amd.h): exact only; */
+#define SEEQ_TLIB_MODE_SUBST 1                              /* ... or one substitution (max_mismatch 1); */
+#define SEEQ_TLIB_MODE_EDIT  2                              /* ... or one edit: a substitution, an insertion or a deletion */
+
+#define SEEQ_TLIB_BY_SUBST  0                               /* the class of the neighbour a corrected span was found by: of its own length; */
+#define SEEQ_TLIB_BY_INS    1                               /* ... one base longer (the read lost a base); */
+#define SEEQ_TLIB_BY_DEL    2                               /* ... one base shorter (the read carries one base too many) */
+#define SEEQ_TLIB_INS_LEN_MAX 30                            /* the longest key with insertion neighbours: a key of 32 bases does not exist */
+#define SEEQ_TLIB_EDIT_SEARCHES 8                           /* searches of a lane of the edit pass: 3 substitutions, 1 deletion, 4 insertions */
+
 #define SEEQ_TLIB_E_NOKEY   1                               /* tally_lib_prepare: a value that is no key; a duplicate; too many entries */
 #define SEEQ_TLIB_E_DUP     2
 #define SEEQ_TLIB_E_MANY    3
 
 /* the neighbour of a key of len bases: another base, s in {1, 2, 3}, at position p < len */
 SEEQ_ST_HD uint64_t tally_neighbour(uint64_t key, uint32_t len, uint32_t p, uint32_t s) { return key ^ ((uint64_t)s << (2u * (len - 1u - p))); }
+
+/* base p < len of a key of len bases: its code (A C T G = 0 1 2 3) */
+SEEQ_ST_HD uint32_t tally_key_base(uint64_t key, uint32_t len, uint32_t p) { return (uint32_t)(key >> (2u * (len - 1u - p))) & 3u; }
+
+/* THE DELETION NEIGHBOUR of a key of len >= 1 bases: base p < len removed, len - 1 bases.  Removing any base of a run of equal bases gives
+   the same key: tally_del_canonical names one position per run, its first. */
+SEEQ_ST_HD uint64_t tally_del_neighbour(uint64_t key, uint32_t len, uint32_t p)
+{
+   const uint32_t low = 2u * (len - 1u - p);                /* bits of the bases behind p */
+   return ((key >> (low + 2u)) << low) | (key & ((1ull << low) - 1ull));
+}
+
+SEEQ_ST_HD int tally_del_canonical(uint64_t key, uint32_t len, uint32_t p) { return p == 0u || tally_key_base(key, len, p) != tally_key_base(key, len, p - 1u); }
+
+/* THE INSERTION NEIGHBOUR of a key of len <= SEEQ_TLIB_INS_LEN_MAX bases: base c in front of position p <= len, len + 1 bases.  Putting a
+   base in front of or behind an equal one gives the same key: tally_ins_canonical keeps the one in front of the run, 3 len + 4 in all. */
+SEEQ_ST_HD uint64_t tally_ins_neighbour(uint64_t key, uint32_t len, uint32_t p, uint32_t c)
+{
+   const uint32_t low = 2u * (len - p);                     /* bits of the bases from p on */
+   return ((((key >> low) << 2) | (uint64_t)c) << low) | (key & ((1ull << low) - 1ull));
+}
+
+SEEQ_ST_HD int tally_ins_canonical(uint64_t key, uint32_t len, uint32_t p, uint32_t c) { return p == 0u || c != tally_key_base(key, len, p - 1u); }
 
 SEEQ_ST_HD uint32_t tally_lib_bitlen(uint64_t n) { return n ? 64u - (uint32_t)__builtin_clzll(n) : 0u; }
 
@@ -170,6 +225,42 @@ SEEQ_ST_HD uint32_t tally_lib_assign(const uint64_t *lkey, const uint32_t *lid, 
    return 0u;
 }
 
+/* The assignment under a MODE (SEEQ_TLIB_MODE_*): modes 0 and 1 are tally_lib_assign with that max_mismatch; mode 2 counts the entries
+   among the neighbours of all three classes.  *by: the class of the one neighbour found (SEEQ_TLIB_BY_*) of a corrected span, else -1. */
+SEEQ_ST_HD uint32_t tally_lib_assign_mode(const uint64_t *lkey, const uint32_t *lid, uint32_t n, uint32_t probes, uint64_t key, int mode, int *kind, int *by)
+{
+   *by = -1;
+   if (mode != SEEQ_TLIB_MODE_EDIT) {
+      const uint32_t id = tally_lib_assign(lkey, lid, n, probes, key, mode, kind);
+      if (*kind == SEEQ_TLIB_CORRECTED) *by = SEEQ_TLIB_BY_SUBST;
+      return id;
+   }
+   const uint32_t id = tally_lib_find(lkey, lid, n, probes, key);
+   if (id) { *kind = SEEQ_TLIB_EXACT; return id; }
+   const uint32_t len = (uint32_t)tally_key_len(key);
+   uint32_t nfound = 0, found = 0;
+   for (uint32_t p = 0; p < len; p++) {
+      for (uint32_t s = 1; s <= 3u; s++) {
+         const uint32_t h = tally_lib_find(lkey, lid, n, probes, tally_neighbour(key, len, p, s));
+         if (h) { nfound++; found = h; *by = SEEQ_TLIB_BY_SUBST; }
+      }
+      if (tally_del_canonical(key, len, p)) {
+         const uint32_t h = tally_lib_find(lkey, lid, n, probes, tally_del_neighbour(key, len, p));
+         if (h) { nfound++; found = h; *by = SEEQ_TLIB_BY_DEL; }
+      }
+   }
+   for (uint32_t p = 0; p <= len && len <= SEEQ_TLIB_INS_LEN_MAX; p++)
+      for (uint32_t c = 0; c <= 3u; c++) {
+         if (!tally_ins_canonical(key, len, p, c)) continue;
+         const uint32_t h = tally_lib_find(lkey, lid, n, probes, tally_ins_neighbour(key, len, p, c));
+         if (h) { nfound++; found = h; *by = SEEQ_TLIB_BY_INS; }
+      }
+   *kind = nfound == 1u ? SEEQ_TLIB_CORRECTED : nfound >= 2u ? SEEQ_TLIB_AMBIGUOUS : SEEQ_TLIB_UNKNOWN;
+   if (nfound == 1u) return found;
+   *by = -1;
+   return 0u;
+}
+
 #include <algorithm>
 
 /* The library as the device holds it: skey[0 .. n) the keys ascending, sid[0 .. n) their ids (position in `keys` + 1).  0: done;
@@ -200,7 +291,7 @@ struct TallyLibCnt {
    uint32_t nexact, nmiss;            /* k_tally_assign_top: spans found in the library; nonzero keys that were not */
    uint32_t ncorrected, nambiguous, nunknown;      /* k_tally_near_top: what the misses were */
    uint32_t bad;                      /* 2: an index outside an array (an internal error) */
-   uint32_t pad[2];
+   uint32_t ninserted, ndeleted;      /* k_tally_near_top, the edit mode: the corrected that were found by an insertion, by a deletion */
 };
 
 struct TallyLibArgs {
@@ -217,6 +308,7 @@ struct TallyLibArgs {
    uint32_t        nmiss;
    uint32_t        nwg;               /* workgroups of k_tally_assign_near: one per SEEQ_TLIB_NEAR_WG * SEEQ_TLIB_NEAR_ROUNDS misses */
    uint4          *nstat;             /* [nwg] {corrected, ambiguous, unknown, bad} */
+   uint2          *nedit;             /* [nwg] the edit mode: {inserted, deleted} of the corrected; NULL otherwise */
    TallyLibCnt    *cnt;
 };
 
@@ -290,15 +382,23 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_miss_apply(TallyLibArgs 
    }
 }
 
-__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_assign_near(TallyLibArgs a)
+/* THE NEAR PASS, in its two instances: EDIT false -- the substitutions of max_mismatch 1; EDIT true -- the three classes of one edit.
+   Lane p of a half-wave owns what happens AT position p of its miss: the three substitutions (p < L); under EDIT the deletion of base p
+   (p < L, canonical) and the insertions in front of p (p <= L <= 30, canonical: four for lane 0, three for the others) as well -- at
+   most SEEQ_TLIB_EDIT_SEARCHES searches, stepped together.  Under EDIT a found neighbour adds 1 + (its class << 16) to nfound: the half's
+   sum holds the entries found below, and above them the class of the one that was found alone. */
+template <bool EDIT>
+__device__ __forceinline__ void tally_assign_near(const TallyLibArgs &a)
 {
-   __shared__ uint32_t s_st[4][SEEQ_TILE_WAVES];
+   constexpr int NS = EDIT ? SEEQ_TLIB_EDIT_SEARCHES : 3;
+   constexpr int NST = EDIT ? 6 : 4;
+   __shared__ uint32_t s_st[NST][SEEQ_TILE_WAVES];
    __shared__ uint64_t s_top[SEEQ_TLIB_TOP];
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
    const uint32_t p = threadIdx.x & 31u;                    /* the position this lane varies */
    s_top[threadIdx.x] = tally_lib_sample(a.lkey, a.nlib, a.stride, threadIdx.x);
    __syncthreads();
-   uint32_t ncor = 0, namb = 0, nunk = 0;                   /* wave-uniform */
+   uint32_t ncor = 0, namb = 0, nunk = 0, nins = 0, ndel = 0;      /* wave-uniform */
    bool bad = false;
 #pragma unroll 1
    for (int r = 0; r < SEEQ_TLIB_NEAR_ROUNDS; r++) {
@@ -319,18 +419,33 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_assign_near(TallyLibArgs
          }
       }
       const bool mine = len > 0 && p < (uint32_t)len;
-      uint64_t nb[3];
-      uint32_t lo[3], hi[3];
+      uint64_t nb[NS];
+      uint32_t lo[NS], hi[NS];
 #pragma unroll
       for (int s = 0; s < 3; s++) {
          nb[s] = mine ? tally_neighbour(key, (uint32_t)len, p, (uint32_t)s + 1u) : 0u;
          tally_lib_top_range(s_top, a.nlib, a.stride, nb[s], &lo[s], &hi[s]);
          if (!mine) lo[s] = hi[s] = 0u;
       }
+      uint32_t on = mine ? 7u : 0u;                         /* the searches of this lane that are neighbours, by slot */
+      if constexpr (EDIT) {
+         const bool grows = len >= 0 && len <= SEEQ_TLIB_INS_LEN_MAX && p <= (uint32_t)len;
+         const uint32_t prev = p && (mine || grows) ? tally_key_base(key, (uint32_t)len, p - 1u) : 4u;      /* the base in front of p; 4: none */
+         if (mine && tally_key_base(key, (uint32_t)len, p) != prev) on |= 8u;
+#pragma unroll
+         for (uint32_t c = 0; c < 4u; c++) on |= grows && c != prev ? 16u << c : 0u;
+#pragma unroll
+         for (int s = 3; s < NS; s++) {
+            const bool use = (on >> s) & 1u;
+            nb[s] = !use ? 0u : s == 3 ? tally_del_neighbour(key, (uint32_t)len, p) : tally_ins_neighbour(key, (uint32_t)len, p, (uint32_t)s - 4u);
+            tally_lib_top_range(s_top, a.nlib, a.stride, nb[s], &lo[s], &hi[s]);
+            if (!use) lo[s] = hi[s] = 0u;
+         }
+      }
 #pragma unroll 1
       for (uint32_t it = 0; it < a.probes; it++) {
 #pragma unroll
-         for (int s = 0; s < 3; s++) {
+         for (int s = 0; s < NS; s++) {
             tally_bound_step(a.lkey, 1u, nb[s], &lo[s], &hi[s]);      /* (mid < hi <= nlib) */
          }
       }
@@ -339,11 +454,22 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_assign_near(TallyLibArgs
       for (int s = 0; s < 3; s++) {
          if (mine && lo[s] < a.nlib && a.lkey[lo[s]] == nb[s]) { nfound++; idsum += a.lid[lo[s]]; }
       }
+      if constexpr (EDIT) {
+#pragma unroll
+         for (int s = 3; s < NS; s++) {
+            if (((on >> s) & 1u) && lo[s] < a.nlib && a.lkey[lo[s]] == nb[s]) {
+               nfound += 1u + ((uint32_t)(s == 3 ? SEEQ_TLIB_BY_DEL : SEEQ_TLIB_BY_INS) << 16);      /* (at most 256 found in a half) */
+               idsum += a.lid[lo[s]];
+            }
+         }
+      }
 #pragma unroll
       for (int d = 16; d >= 1; d >>= 1) {                   /* (distances below 32 stay inside the half) */
          nfound += (uint32_t)__shfl_xor((int)nfound, d, 64);
          idsum += (uint32_t)__shfl_xor((int)idsum, d, 64);
       }
+      const uint32_t by = EDIT ? nfound >> 16 : 0u;
+      if constexpr (EDIT) nfound &= 0xFFFFu;
       int kind = -1;
       if (here && p == 0u) {
          kind = nfound == 1u ? SEEQ_TLIB_CORRECTED : nfound >= 2u ? SEEQ_TLIB_AMBIGUOUS : SEEQ_TLIB_UNKNOWN;
@@ -352,40 +478,60 @@ __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_assign_near(TallyLibArgs
       ncor += (uint32_t)__popcll(__ballot(kind == SEEQ_TLIB_CORRECTED));
       namb += (uint32_t)__popcll(__ballot(kind == SEEQ_TLIB_AMBIGUOUS));
       nunk += (uint32_t)__popcll(__ballot(kind == SEEQ_TLIB_UNKNOWN));
+      if constexpr (EDIT) {
+         nins += (uint32_t)__popcll(__ballot(kind == SEEQ_TLIB_CORRECTED && by == SEEQ_TLIB_BY_INS));
+         ndel += (uint32_t)__popcll(__ballot(kind == SEEQ_TLIB_CORRECTED && by == SEEQ_TLIB_BY_DEL));
+      }
    }
    const uint32_t nbad = __ballot(bad) != 0ull ? 2u : 0u;
-   if (lane == 0) { s_st[0][wave] = ncor; s_st[1][wave] = namb; s_st[2][wave] = nunk; s_st[3][wave] = nbad; }
+   if (lane == 0) {
+      s_st[0][wave] = ncor; s_st[1][wave] = namb; s_st[2][wave] = nunk; s_st[3][wave] = nbad;
+      if constexpr (EDIT) { s_st[4][wave] = nins; s_st[5][wave] = ndel; }
+   }
    __syncthreads();
    if (threadIdx.x == 0) {
       uint4 t = make_uint4(0u, 0u, 0u, 0u);
       for (int w = 0; w < SEEQ_TILE_WAVES; w++) { t.x += s_st[0][w]; t.y += s_st[1][w]; t.z += s_st[2][w]; t.w |= s_st[3][w]; }
       a.nstat[blockIdx.x] = t;
+      if constexpr (EDIT) {
+         uint2 e = make_uint2(0u, 0u);
+         for (int w = 0; w < SEEQ_TILE_WAVES; w++) { e.x += s_st[4][w]; e.y += s_st[5][w]; }
+         a.nedit[blockIdx.x] = e;
+      }
    }
 }
 
-/* One workgroup: the near workgroups' {corrected, ambiguous, unknown, bad} -> the totals. */
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_assign_near(TallyLibArgs a) { tally_assign_near<false>(a); }
+
+__global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_assign_near_edit(TallyLibArgs a) { tally_assign_near<true>(a); }
+
+/* One workgroup: the near workgroups' {corrected, ambiguous, unknown, bad}, and {inserted, deleted} under the edit mode -> the totals. */
 __global__ __launch_bounds__(SEEQ_TILE_WG) void k_tally_near_top(TallyLibArgs a)
 {
    __shared__ uint32_t s_wave[SEEQ_TILE_WAVES], s_bad[SEEQ_TILE_WAVES];
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   uint32_t ncor = 0, namb = 0, nunk = 0, bad = 0;
+   uint32_t ncor = 0, namb = 0, nunk = 0, nins = 0, ndel = 0, bad = 0;
    for (uint32_t b0 = 0; b0 < a.nwg; b0 += SEEQ_TILE_WG) {
       const uint32_t i = b0 + threadIdx.x;
       if (i < a.nwg) {
          const uint4 t = a.nstat[i];
          ncor += t.x; namb += t.y; nunk += t.z; bad |= t.w;
+         if (a.nedit) { const uint2 e = a.nedit[i]; nins += e.x; ndel += e.y; }
       }
    }
-   uint32_t tot_cor, tot_amb, tot_unk;
+   uint32_t tot_cor, tot_amb, tot_unk, tot_ins, tot_del;
    block_excl_scan(ncor, &tot_cor, s_wave);
    block_excl_scan(namb, &tot_amb, s_wave);
    block_excl_scan(nunk, &tot_unk, s_wave);
+   block_excl_scan(nins, &tot_ins, s_wave);
+   block_excl_scan(ndel, &tot_del, s_wave);
    bad = __ballot(bad != 0u) != 0ull ? 2u : 0u;
    if (lane == 0) s_bad[wave] = bad;
    __syncthreads();
    if (threadIdx.x == 0) {
       for (int w = 0; w < SEEQ_TILE_WAVES; w++) bad |= s_bad[w];
       a.cnt->ncorrected = tot_cor; a.cnt->nambiguous = tot_amb; a.cnt->nunknown = tot_unk; a.cnt->bad = bad;
+      a.cnt->ninserted = tot_ins; a.cnt->ndeleted = tot_del;
    }
 }
 

@@ -2,8 +2,9 @@
  * seeq_tally_library_host.h -- the host driver of the tally against a known library (rule and kernels: seeq_tally_library.h): the set
  * call's validation, sort and upload, the assignment of a key array in place -- the exact pass, and under max_mismatch 1 the compaction of
  * the misses and the near pass -- as the step of tally_run (seeq_tally_host.h) between its pack and its sort, or behind the grouped
- * tally's hold, and the seeqdevScanSetLibrary / seeqdevScanTallyLibrary / seeqdevScanTallyHoldLibrary entries.  Included by seeq_device.hip behind
- * seeq_tally_group_host.h.
+ * tally's hold, and the seeqdevScanSetLibrary / seeqdevScanSetLibraryMode / seeqdevScanLastLibraryEdits / seeqdevScanTallyLibrary /
+ * seeqdevScanTallyHoldLibrary entries.  Under the edit mode (SEEQDEV_LIBRARY_EDIT) the near pass is its second instance, and the split of
+ * the corrected spans is kept on the context.  Included by seeq_device.hip behind seeq_tally_group_host.h.
  */
 #ifndef SEEQ_TALLY_LIBRARY_HOST_H_
 #define SEEQ_TALLY_LIBRARY_HOST_H_
@@ -14,20 +15,22 @@ static int tally_library_fail(const char *what, const TallyLibCnt &l, const Tall
 {
    snprintf(g_last_error, sizeof g_last_error,
             "internal inconsistency in the library tally (%s: flags %u / %u, %u spans, %llu with a key, %u exact, %u misses, %u corrected, %u ambiguous, %u unknown, "
-            "%llu assigned, %u nonzero ids, %u distinct of %zu entries, first head %u)",
-            what, l.bad, h.bad, n, (unsigned long long)nkeyed, l.nexact, l.nmiss, l.ncorrected, l.nambiguous, l.nunknown, (unsigned long long)nassigned, h.nonzero,
-            h.ndistinct, nlib, h.first);
+            "%u inserted, %u deleted, %llu assigned, %u nonzero ids, %u distinct of %zu entries, first head %u)",
+            what, l.bad, h.bad, n, (unsigned long long)nkeyed, l.nexact, l.nmiss, l.ncorrected, l.nambiguous, l.nunknown, l.ninserted, l.ndeleted,
+            (unsigned long long)nassigned, h.nonzero, h.ndistinct, nlib, h.first);
    errno = EIO;
    return -1;
 }
 
-extern "C" int seeqdevScanSetLibrary(seeqdev_scan_t *s, const uint64_t *keys, size_t n, int max_mismatch)
+extern "C" int seeqdevScanSetLibraryMode(seeqdev_scan_t *s, const uint64_t *keys, size_t n, int mode)
 {
    seeqerr = 0;
    if (!s) { errno = EINVAL; return -1; }
    s->lb_n = 0;                                            /* (the library of before is gone, whatever comes of this call) */
    s->lb_mismatch = 0;
-   if ((!keys && n) || (max_mismatch != 0 && max_mismatch != 1)) { errno = EINVAL; return -1; }
+   s->lb_mode = SEEQDEV_LIBRARY_EXACT;
+   memset(&s->lb_edits, 0, sizeof s->lb_edits);
+   if ((!keys && n) || (mode != SEEQDEV_LIBRARY_EXACT && mode != SEEQDEV_LIBRARY_SUBST && mode != SEEQDEV_LIBRARY_EDIT)) { errno = EINVAL; return -1; }
    if (!n) return 0;
    if (n > SEEQ_TLIB_MAX) {
       snprintf(g_last_error, sizeof g_last_error, "library: %zu entries, at most %u", n, SEEQ_TLIB_MAX);
@@ -50,7 +53,21 @@ extern "C" int seeqdevScanSetLibrary(seeqdev_scan_t *s, const uint64_t *keys, si
    HIP_TRY(hipMemcpyAsync(s->lb_id, sid.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream), EIO);
    HIP_TRY(hipStreamSynchronize(s->stream), EIO);            /* (the host copies go with this call) */
    s->lb_n = n;
-   s->lb_mismatch = max_mismatch;
+   s->lb_mismatch = mode != SEEQDEV_LIBRARY_EXACT;
+   s->lb_mode = mode;
+   return 0;
+}
+
+/* (max_mismatch 0 and 1 ARE the modes SEEQDEV_LIBRARY_EXACT and _SUBST; any other value is no mode) */
+extern "C" int seeqdevScanSetLibrary(seeqdev_scan_t *s, const uint64_t *keys, size_t n, int max_mismatch)
+{
+   return seeqdevScanSetLibraryMode(s, keys, n, max_mismatch == 0 || max_mismatch == 1 ? max_mismatch : -1);
+}
+
+extern "C" int seeqdevScanLastLibraryEdits(const seeqdev_scan_t *s, seeqdev_tally_library_edits_t *out)
+{
+   if (!s || !out) { errno = EINVAL; return -1; }
+   *out = s->lb_edits;
    return 0;
 }
 
@@ -59,6 +76,8 @@ extern "C" int seeqdevScanSetLibrary(seeqdev_scan_t *s, const uint64_t *keys, si
 static int tally_library_assign(seeqdev_scan *s, uint64_t *key, uint32_t *miss, uint32_t n, uint64_t nkeyed, TallyLibCnt *l)
 {
    const hipStream_t st = s->stream;
+   const bool edit = s->lb_mode == SEEQDEV_LIBRARY_EDIT;
+   memset(&s->lb_edits, 0, sizeof s->lb_edits);             /* (a failed assignment leaves no split) */
    const size_t nt = (size_t)tally_tiles(n);
    if (ws_make(&s->ws, {{s->d_lbcnt, sizeof(TallyLibCnt)}, {s->h_lbcnt, sizeof(TallyLibCnt), WS_PINNED}})) return -1;
    if (ws_grow(&s->ws, &s->cap_lb_sum, nt, {{s->lb_sum, 2 * nt * sizeof(uint32_t)}})) return -1;
@@ -89,18 +108,29 @@ static int tally_library_assign(seeqdev_scan *s, uint64_t *key, uint32_t *miss, 
    a.nwg = (uint32_t)(((uint64_t)a.nmiss + SEEQ_TLIB_NEAR_WG * SEEQ_TLIB_NEAR_ROUNDS - 1) / (SEEQ_TLIB_NEAR_WG * SEEQ_TLIB_NEAR_ROUNDS));
    if (ws_grow(&s->ws, &s->cap_lb_near, a.nwg, {{s->lb_nstat, (size_t)a.nwg * sizeof(uint4)}})) return -1;
    a.nstat = s->lb_nstat;
-   if ((size_t)a.nwg > s->cap_lb_near) {
-      snprintf(g_last_error, sizeof g_last_error, "library tally: %u workgroups of the near pass, room for %zu", a.nwg, s->cap_lb_near);
+   if (edit) {                                             /* the edit instance's two further counts per workgroup */
+      if (ws_grow(&s->ws, &s->cap_lb_edit, a.nwg, {{s->lb_nedit, (size_t)a.nwg * sizeof(uint2)}})) return -1;
+      a.nedit = s->lb_nedit;
+   }
+   if ((size_t)a.nwg > s->cap_lb_near || (edit && (size_t)a.nwg > s->cap_lb_edit)) {
+      snprintf(g_last_error, sizeof g_last_error, "library tally: %u workgroups of the near pass, room for %zu%s", a.nwg, edit ? s->cap_lb_edit : s->cap_lb_near,
+               edit ? " (the edit counts)" : "");
       errno = EIO;
       return -1;
    }
    hipLaunchKernelGGL(k_tally_miss_apply, dim3(a.nt), dim3(SEEQ_TILE_WG), 0, st, a);
-   hipLaunchKernelGGL(k_tally_assign_near, dim3(a.nwg), dim3(SEEQ_TILE_WG), 0, st, a);
+   if (edit) hipLaunchKernelGGL(k_tally_assign_near_edit, dim3(a.nwg), dim3(SEEQ_TILE_WG), 0, st, a);
+   else hipLaunchKernelGGL(k_tally_assign_near, dim3(a.nwg), dim3(SEEQ_TILE_WG), 0, st, a);
    hipLaunchKernelGGL(k_tally_near_top, dim3(1), dim3(SEEQ_TILE_WG), 0, st, a);
    if (counters_fetch(s, s->h_lbcnt, s->d_lbcnt, sizeof(TallyLibCnt))) return -1;
    *l = *s->h_lbcnt;
    if (l->bad || (uint64_t)l->nexact + l->nmiss != nkeyed || (uint64_t)l->ncorrected + l->nambiguous + l->nunknown != l->nmiss)
       return tally_library_fail("near", *l, none, n, nkeyed, 0, s->lb_n);
+   if ((uint64_t)l->ninserted + l->ndeleted > l->ncorrected || (!edit && (l->ninserted || l->ndeleted)))      /* (nsubstituted is the rest of ncorrected) */
+      return tally_library_fail("edits", *l, none, n, nkeyed, 0, s->lb_n);
+   s->lb_edits.nsubstituted = (uint64_t)l->ncorrected - l->ninserted - l->ndeleted;
+   s->lb_edits.ninserted = l->ninserted;
+   s->lb_edits.ndeleted = l->ndeleted;
    return 0;
 }
 
@@ -166,6 +196,7 @@ extern "C" int seeqdevScanTallyLibrary(seeqdev_scan_t *s, int source, const void
    const uint64_t *off;
    uint64_t n;
    if (tally_enter(s, counts, source, tally_library_missing(s), &d_text, &nbytes, &rec, &off, &n)) return -1;
+   memset(&s->lb_edits, 0, sizeof s->lb_edits);             /* (no span with a key: no assignment, and no split of one before) */
    s->tl_n = 0;                                            /* (the table of the tally before, of either kind, is gone, whatever comes of this one) */
    s->tm_tl.ms = 0.f;
    return tally_library_run(s, rec, off, (uint32_t)n, d_text, nbytes, counts);
@@ -177,6 +208,7 @@ extern "C" int seeqdevScanTallyHoldLibrary(seeqdev_scan_t *s, int source, const 
    const uint64_t *off;
    uint64_t n;
    if (tally_enter(s, counts, source, tally_library_missing(s), &d_text, &nbytes, &rec, &off, &n)) return -1;
+   memset(&s->lb_edits, 0, sizeof s->lb_edits);             /* (no span with a key: no assignment, and no split of one before) */
    tally_hold_reset(s);
    seeqdev_tally_hold_counts_t held;
    if (tally_hold_run(s, rec, off, (uint32_t)n, false, d_text, nbytes, &held, tally_hold_target(s))) return -1;

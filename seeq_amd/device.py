@@ -569,19 +569,35 @@ class Scanner:
         return float(ms.value)
 
     # ---- counting against a known library (include/seeq_amd.h: seeqdevScanSetLibrary / seeqdevScanTallyLibrary / seeqdevScanTallyHoldLibrary) ----
-    def set_library(self, sequences, max_mismatch=1):
+    def set_library(self, sequences, max_mismatch=1, indels=False):
         """Give this Scanner a library of known sequences -- guides, a barcode whitelist: str or bytes of at most 31 bases ACGTU each, or
         an integer array of tally keys.  Entry i has the id i + 1.  max_mismatch 1: a span one substitution away from exactly one entry
-        counts for it; 0: exact only.  The library stays with the Scanner until the next set_library or clear_library; an empty one
-        clears it.  ValueError for a sequence that has no key, SeeqDeviceError for a duplicate."""
+        counts for it; 0: exact only.  indels=True (with max_mismatch 1): one EDIT away -- a substitution, or one base lost or gained
+        (seeqdevScanSetLibraryMode, SEEQDEV_LIBRARY_EDIT); library_edits() then splits the corrected spans by the kind of the edit.  The
+        library stays with the Scanner until the next set_library or clear_library; an empty one clears it.  ValueError for a sequence
+        that has no key and for indels with max_mismatch 0, SeeqDeviceError for a duplicate."""
+        if indels and int(max_mismatch) != 1:
+            raise ValueError("indels=True is one edit: it goes with max_mismatch=1, not %r" % (max_mismatch,))
         if isinstance(sequences, np.ndarray):
             keys = np.ascontiguousarray(sequences, dtype=np.uint64)
         else:
             keys = np.array([q if isinstance(q, (int, np.integer)) else tally_key(q) for q in sequences], dtype=np.uint64)
-        _check(self._lib.seeqdevScanSetLibrary(self._h, keys.ctypes.data if len(keys) else None, len(keys), int(max_mismatch)))
+        if indels:
+            _check(self._lib.seeqdevScanSetLibraryMode(self._h, keys.ctypes.data if len(keys) else None, len(keys), _capi.SEEQDEV_LIBRARY_EDIT))
+        else:
+            _check(self._lib.seeqdevScanSetLibrary(self._h, keys.ctypes.data if len(keys) else None, len(keys), int(max_mismatch)))
 
     def clear_library(self):
         _check(self._lib.seeqdevScanSetLibrary(self._h, None, 0, 0))
+
+    def library_edits(self):
+        """The corrected spans of the last library assignment (tally_library, tally_hold_library, tally_hold_append(library=True)) by the
+        kind of their one edit -> dict(nsubstituted, ninserted, ndeleted), summing to its ncorrected: the entry has the span's length, is
+        one base longer (the read lost a base), is one base shorter (the read gained one).  All zero after set_library and before any
+        assignment; without indels, ninserted = ndeleted = 0."""
+        e = _capi.seeqdev_tally_library_edits_t()
+        _check(self._lib.seeqdevScanLastLibraryEdits(self._h, C.byref(e)))
+        return dict(nsubstituted=int(e.nsubstituted), ninserted=int(e.ninserted), ndeleted=int(e.ndeleted))
 
     @staticmethod
     def _library_counts(cnt):
