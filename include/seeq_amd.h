@@ -712,6 +712,74 @@ int seeqdevScanCopyHeld(seeqdev_scan_t * scan, uint32_t * lines_out, uint64_t * 
  * with bits above them, a NULL pointer. */
 int seeqdevTallySplit(uint64_t key, const uint32_t * widths, int ncolumns, uint64_t * out);
 
+/* THE TALLY OF THE HELD COLUMN ITSELF: SAMPLE x GUIDE WITH NO UMI.  The bulk pooled screen counts reads per (sample barcode, guide) and has
+ * no member column: the held word a hold and its appends composed IS the key.  seeqdevScanTallyHeld counts the distinct held words, one per
+ * line, ON THE DEVICE (seeq_tally_held.h), and seeqdevScanTallyHeldDense scatters the result into the dense matrix a screen wants.  It covers
+ * (cell, guide) and (sample, whitelist id, guide) alike.
+ *   kind of a held record    record i OPENS its line iff i == 0 or the record before it has another line number.  REPEAT: it does not open
+ *                            its line.  KEYLESS: it opens its line and has key 0.  COUNTED: it opens its line and has a key.  A line is
+ *                            counted at most once and its FIRST held record decides (the grouped call's rule): a line whose first record
+ *                            has no key is not counted, even when a later record of it has one.  nrecords = ncounted + nkeyless + nrepeat.
+ *   member_columns m         0 <= m < the held key's columns: shift = the sum of the widths of the LAST m columns
+ *                            (seeqdevScanTallyHoldColumns); the row of a key is key >> shift, its column part key & ((1 << shift) - 1).
+ *                            m == 0: shift 0 and no row table.
+ *   THE KEY TABLE            is the context's tally table, exactly as seeqdevScanTallyLibrary's: one seeqdev_tally_t {key = the held word,
+ *                            count} per distinct counted word, ascending, the counts summing to ncounted -- served by
+ *                            seeqdevScanTallyDevice / seeqdevScanCopyTally and replaced by the next tally of any kind.  The sparse matrix
+ *                            in row order.
+ *   THE ROW TABLE            (m >= 1) one seeqdev_tally_group_t per distinct row, ascending: group = key >> shift, count = its reads,
+ *                            first = the rank of its first entry in the key table, ndistinct = its entries -- [first, first + ndistinct).
+ *                            Served by seeqdevScanTallyHeldRowsDevice / seeqdevScanCopyTallyHeldRows, valid until the next held tally.
+ *   passes                   ceil(key_bits / 8) of the tally's single-word sort, key_bits the bit length of the largest held key (what the
+ *                            hold or the last append reported); 0 when nothing is counted.  counts->key_bits: of the largest COUNTED key.
+ *   seeqdevScanTallyHeldDense  d_out: nrows * ncols uint64_t of device memory, row-major, ALL of them written: zero-filled, then for every
+ *                            entry of the key table with r = key >> shift and c = the column part: inside iff 1 <= r <= nrows and
+ *                            1 <= c <= ncols, cell (r - 1) * ncols + (c - 1) = count.  Demux keys (pattern + 1) and library ids are
+ *                            1-based: that is what the matrix is for; raw sequence columns fall outside and the sparse tables serve them.
+ *                            ninside + noutside = ndistinct, inside_reads + outside_reads = ncounted.  It runs on the context's stream.
+ *                            seeqdevTallyHeldCell is the same rule on the host (no GPU): 1 and *cell, 0 for a key outside, -1 / EINVAL for
+ *                            a NULL cell or a shift beyond 63.
+ * Both calls are synchronous.  seeqdevScanTallyHeld: EINVAL, before any device call, for a NULL scan or counts, a context without a
+ * completed hold, member_columns < 0 or >= the columns of the held key.  A hold of zero records, or one with nothing counted, is a valid
+ * empty result: the tables are empty and nothing is launched beyond the pack.  EIO: an internal inconsistency (seeqdevLastError names the
+ * numbers).  seeqdevScanTallyHeldDense, the arguments first: EINVAL for a NULL argument and for nrows == 0 or ncols == 0, E2BIG for more than
+ * SEEQDEV_TALLY_DENSE_MAX (2^28) cells; then EINVAL for a context whose tally table is not (or no longer: a plain or library tally since)
+ * that of a completed held tally, and for a held tally with member_columns 0 -- all before any device call.
+ * The held tally reads the held column and writes the tally's key scratch and table and arrays of its own: the held column and its columns,
+ * the grouped call's two tables, the collapse's result, the inserts result, the record arrays, the fetch state, the library and the gate's
+ * and the anchor's arrays are afterwards what they were.
+ * Device memory of its own: 12 bytes per tile of 1 024 held records, 24 per distinct row, 12 per 256 entries of the key table (the dense
+ * call), beside the plain tally's scratch and table.  (The reference counts nothing: an addition of this boundary.) */
+#define SEEQDEV_TALLY_DENSE_MAX ((uint64_t)1 << 28)   /* cells of a dense matrix: 2 GiB */
+typedef struct {
+   uint64_t nrecords;         /* records of the held column */
+   uint64_t ncounted;         /* of them: the first of their line, with a key -- the sum of the key table's counts */
+   uint64_t nkeyless;         /* the first of their line, without a key */
+   uint64_t nrepeat;          /* not the first of their line */
+   uint64_t ndistinct;        /* entries of the key table */
+   uint64_t nrows;            /* entries of the row table; 0 for member_columns 0 */
+   uint32_t key_bits;         /* the bit length of the largest counted key */
+   uint32_t shift;            /* bits of the column part */
+   uint32_t passes;           /* passes of the sort; 0: nothing counted */
+   uint32_t member_columns;
+} seeqdev_tally_held_counts_t;   /* 64 bytes */
+
+typedef struct {
+   uint64_t ninside;          /* entries of the key table inside the matrix */
+   uint64_t noutside;
+   uint64_t inside_reads;     /* the sum of the matrix */
+   uint64_t outside_reads;
+} seeqdev_tally_dense_counts_t;   /* 32 bytes */
+
+int seeqdevScanTallyHeld(seeqdev_scan_t * scan, int member_columns, seeqdev_tally_held_counts_t * counts);
+const seeqdev_tally_group_t * seeqdevScanTallyHeldRowsDevice(const seeqdev_scan_t * scan);
+int seeqdevScanCopyTallyHeldRows(seeqdev_scan_t * scan, seeqdev_tally_group_t * host_out, size_t first, size_t n);
+int seeqdevScanTallyHeldDense(seeqdev_scan_t * scan, void * d_out, uint32_t nrows, uint32_t ncols, seeqdev_tally_dense_counts_t * counts);
+/* Device time (ms) of the last held tally or dense call, whichever came last -- its launches and counter copies, between two HIP events on
+ * the context's stream (profiling on; 0 otherwise, and when there was no record). */
+int seeqdevScanLastTallyHeldMs(const seeqdev_scan_t * scan, float * ms);
+int seeqdevTallyHeldCell(uint64_t key, uint32_t shift, uint32_t nrows, uint32_t ncols, uint64_t * cell);
+
 /* THE BASE-QUALITY GATE -- every FASTQ counting pipeline puts a bar on the base qualities of what it counts ("drop the UMI if any base is
  * below Q", "at most k bases below Q in the barcode"): an uncertain base is what makes the spurious distinct keys, the corrected library
  * hits and the absorbed UMI pairs.  seeqdevScanQualityGate reads, ON THE DEVICE, the quality bytes under every span of a record array --

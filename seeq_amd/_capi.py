@@ -139,6 +139,18 @@ class seeqdev_tally_append_counts_t(C.Structure):
 
 
 SEEQDEV_TALLY_COLUMNS = 8           # columns of a held key, the hold's own included
+
+
+class seeqdev_tally_held_counts_t(C.Structure):
+    _fields_ = [("nrecords", C.c_uint64), ("ncounted", C.c_uint64), ("nkeyless", C.c_uint64), ("nrepeat", C.c_uint64), ("ndistinct", C.c_uint64),
+                ("nrows", C.c_uint64), ("key_bits", C.c_uint32), ("shift", C.c_uint32), ("passes", C.c_uint32), ("member_columns", C.c_uint32)]
+
+
+class seeqdev_tally_dense_counts_t(C.Structure):
+    _fields_ = [("ninside", C.c_uint64), ("noutside", C.c_uint64), ("inside_reads", C.c_uint64), ("outside_reads", C.c_uint64)]
+
+
+SEEQDEV_TALLY_DENSE_MAX = 1 << 28   # cells of a dense matrix (seeqdevScanTallyHeldDense)
 SEEQDEV_TALLY_GATED = 4             # the spans the context's last quality gate passed
 SEEQDEV_QGATE_PASS, SEEQDEV_QGATE_LOW, SEEQDEV_QGATE_LONG, SEEQDEV_QGATE_FAR, SEEQDEV_QGATE_MISFIT = 0, 1, 2, 3, 4
 
@@ -183,6 +195,8 @@ EXPORTS = [
     "seeqdevScanCopyTallyCollapse", "seeqdevScanLastTallyCollapseMs",
     "seeqdevScanSetLibrary", "seeqdevScanTallyLibrary", "seeqdevScanTallyHoldLibrary", "seeqdevScanSetLibraryMode", "seeqdevScanLastLibraryEdits",
     "seeqdevScanTallyHoldAppend", "seeqdevScanTallyHoldAppendLibrary", "seeqdevScanTallyHoldColumns", "seeqdevScanCopyHeld", "seeqdevTallySplit",
+    "seeqdevScanTallyHeld", "seeqdevScanTallyHeldRowsDevice", "seeqdevScanCopyTallyHeldRows", "seeqdevScanTallyHeldDense", "seeqdevScanLastTallyHeldMs",
+    "seeqdevTallyHeldCell",
     "seeqdevScanQualityGate", "seeqdevScanGatedDevice", "seeqdevScanCopyGated", "seeqdevScanCopyGatedOffsets", "seeqdevScanCopyGateKinds",
     "seeqdevScanLastQualityGateMs",
     "seeqdevScanAnchor", "seeqdevScanAnchoredDevice", "seeqdevScanCopyAnchored", "seeqdevScanCopyAnchoredOffsets", "seeqdevScanCopyAnchorKinds",
@@ -402,6 +416,18 @@ def lib():
     L.seeqdevScanCopyHeld.restype = C.c_int
     L.seeqdevTallySplit.argtypes = [C.c_uint64, P(C.c_uint32), C.c_int, P(C.c_uint64)]
     L.seeqdevTallySplit.restype = C.c_int
+    L.seeqdevScanTallyHeld.argtypes = [C.c_void_p, C.c_int, P(seeqdev_tally_held_counts_t)]
+    L.seeqdevScanTallyHeld.restype = C.c_int
+    L.seeqdevScanTallyHeldRowsDevice.argtypes = [C.c_void_p]
+    L.seeqdevScanTallyHeldRowsDevice.restype = C.c_void_p
+    L.seeqdevScanCopyTallyHeldRows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+    L.seeqdevScanCopyTallyHeldRows.restype = C.c_int
+    L.seeqdevScanTallyHeldDense.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(seeqdev_tally_dense_counts_t)]
+    L.seeqdevScanTallyHeldDense.restype = C.c_int
+    L.seeqdevScanLastTallyHeldMs.argtypes = [C.c_void_p, P(C.c_float)]
+    L.seeqdevScanLastTallyHeldMs.restype = C.c_int
+    L.seeqdevTallyHeldCell.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint64)]
+    L.seeqdevTallyHeldCell.restype = C.c_int
     L.seeqdevScanQualityGate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(seeqdev_qgate_counts_t)]
     L.seeqdevScanQualityGate.restype = C.c_int
     L.seeqdevScanGatedDevice.argtypes = [C.c_void_p]

@@ -116,6 +116,7 @@ static constexpr size_t SAMPLE_BYTES = 65536;     /* prefix sampled to estimate 
 #include "seeq_tally_append.h"
 #include "seeq_tally_library.h"
 #include "seeq_tally_collapse.h"
+#include "seeq_tally_held.h"
 #include "seeq_qgate.h"
 #include "seeq_anchor.h"
 static_assert(SEEQ_ANCHOR_AFTER == SEEQDEV_ANCHOR_AFTER && SEEQ_ANCHOR_BEFORE == SEEQDEV_ANCHOR_BEFORE && SEEQ_ANCHOR_LINE == SEEQDEV_ANCHOR_LINE &&
@@ -601,6 +602,17 @@ struct seeqdev_scan {
    CollapseCnt *d_tccnt, *h_tccnt;                        /* h_ pinned */
    size_t    tc_np, tc_ng;                                /* entries of the last collapse's two arrays */
    EventPair tm_tc;                                       /* profiling: around the collapse's launches and its counters copy */
+   /* seeqdevScanTallyHeld / seeqdevScanTallyHeldDense (seeq_tally_held.h): the tally of the held column itself.  Its key scratch and its key
+      table are the plain tally's (tl_key0 / tl_key1 / tl_mat; tl_tab: tl_n); the head sums, the row table and the dense call's sums are its own */
+   uint32_t *thd_sum; size_t cap_thd;                     /* per tile: key heads, row heads, nonzero items */
+   seeqdev_tally_group_t *thd_rows; size_t cap_thd_rows;  /* the row table: one entry per distinct row */
+   uint32_t *thd_dn; uint64_t *thd_dr; size_t cap_thd_dense;      /* per 256 entries of the key table: those outside the matrix, their reads */
+   TallyHeldCnt *d_thdcnt, *h_thdcnt;                     /* h_ pinned */
+   size_t    thd_nrows;                                   /* entries of the last held tally's row table */
+   bool      thd_live;                                    /* a held tally has completed and the context's tally table is still its key table */
+   uint32_t  thd_shift, thd_members;                      /* ... its column part's bits and its member_columns */
+   uint64_t  thd_ncounted;                                /* ... and the sum of its counts */
+   EventPair tm_thd;                                      /* profiling: around the held tally's (or the dense call's) launches and counter copies */
    /* seeqdevScanQualityGate (seeq_qgate.h): allocated by the first gate.  It reads a source's record arrays and writes these; the kinds
       (qg_kind: qg_nsrc source records) and the passed records (qg_rec, qg_off: qg_n) are copies, valid until the next gate */
    uint8_t  *qg_kind; uint32_t *qg_bsum; size_t cap_qg;   /* per source record: its kind; per tile: the seven numbers */
@@ -741,7 +753,7 @@ extern "C" void seeqdevScanFree(seeqdev_scan_t *s)
 {
    if (!s) return;
    (void)use_device(s->device);
-   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl, &s->tm_tg, &s->tm_tc, &s->tm_qg, &s->tm_an})
+   for (EventPair *t : {&s->tm_h2d, &s->tm_st, &s->tm_ins, &s->tm_tl, &s->tm_tg, &s->tm_tc, &s->tm_thd, &s->tm_qg, &s->tm_an})
       if (t->made) { (void)hipEventDestroy(t->ev[0]); (void)hipEventDestroy(t->ev[1]); }
    (void)hipStreamSynchronize(s->stream);
    ws_free_all(&s->ws);
@@ -1914,6 +1926,7 @@ extern "C" int seeqdevScanHost(seeqdev_scan_t *s, const seeqdev_pattern_t *pat, 
 #include "seeq_tally_group_host.h"
 #include "seeq_tally_library_host.h"
 #include "seeq_tally_collapse_host.h"
+#include "seeq_tally_held_host.h"
 #include "seeq_qgate_host.h"
 #include "seeq_anchor_host.h"
 

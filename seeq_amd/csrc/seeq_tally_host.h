@@ -233,6 +233,7 @@ extern "C" int seeqdevScanTally(seeqdev_scan_t *s, int source, const void *d_tex
    uint64_t n;
    if (tally_enter(s, counts, source, NULL, &d_text, &nbytes, &rec, &off, &n)) return -1;
    s->tl_n = 0;                                            /* (the table of the call before is gone, whatever comes of this one) */
+   s->thd_live = false;                                    /* (... and it is no held tally's key table any more: seeq_tally_held_host.h) */
    s->tm_tl.ms = 0.f;
    return tally_run(s, rec, off, (uint32_t)n, d_text, nbytes, counts);
 }

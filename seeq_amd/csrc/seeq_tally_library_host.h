@@ -198,6 +198,7 @@ extern "C" int seeqdevScanTallyLibrary(seeqdev_scan_t *s, int source, const void
    if (tally_enter(s, counts, source, tally_library_missing(s), &d_text, &nbytes, &rec, &off, &n)) return -1;
    memset(&s->lb_edits, 0, sizeof s->lb_edits);             /* (no span with a key: no assignment, and no split of one before) */
    s->tl_n = 0;                                            /* (the table of the tally before, of either kind, is gone, whatever comes of this one) */
+   s->thd_live = false;                                    /* (... and it is no held tally's key table any more: seeq_tally_held_host.h) */
    s->tm_tl.ms = 0.f;
    return tally_library_run(s, rec, off, (uint32_t)n, d_text, nbytes, counts);
 }

@@ -35,7 +35,7 @@ struct WsHooks {
    int   (*copy)(void *ctx, int kind, void *dst, const void *src, size_t bytes);
 };
 
-static constexpr int WS_MAX_SLOTS = 136;
+static constexpr int WS_MAX_SLOTS = 144;
 
 struct Workspace {
    WsHooks hooks;

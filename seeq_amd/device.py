@@ -678,6 +678,59 @@ class Scanner:
             _check(self._lib.seeqdevScanCopyHeld(self._h, res["lines"].ctypes.data if n else None, res["keys"].ctypes.data if n else None, 0, n))
         return res
 
+    # ---- the tally of the held column itself (include/seeq_amd.h: seeqdevScanTallyHeld / seeqdevScanTallyHeldDense) ----
+    def tally_held(self, member_columns=0, copy=True):
+        """How often each distinct held word occurs, one count per line (its first held record decides), counted on the device: the
+        bulk screen -- sample x guide with no UMI -- behind tally_hold and tally_hold_append.  member_columns m: the last m columns of
+        the held key are the column part of a key, the ones before them its row (0: no row table).  -> dict: nrecords, ncounted,
+        nkeyless, nrepeat, ndistinct, nrows, key_bits, shift, passes, member_columns; copy adds table (TALLY_DTYPE: the held words
+        ascending with their counts -- this Scanner's tally table, replaced by the next tally of any kind) and rows
+        (TALLY_GROUP_DTYPE: per row its reads, the rank of its first entry in the table and its entries; empty for m == 0).
+        copy=False leaves both on the device (tally_device_ptr / tally_table, tally_held_rows_device_ptr / tally_held_rows_table)."""
+        cnt = _capi.seeqdev_tally_held_counts_t()
+        _check(self._lib.seeqdevScanTallyHeld(self._h, int(member_columns), C.byref(cnt)))
+        res = {name: int(getattr(cnt, name)) for name, _ in _capi.seeqdev_tally_held_counts_t._fields_}
+        if copy:
+            res["table"] = self.tally_table(res["ndistinct"])
+            res["rows"] = self.tally_held_rows_table(res["nrows"])
+        return res
+
+    def tally_held_rows_table(self, n, first=0):
+        """Copy entries [first, first + n) of the last held tally's row table to the host -> structured array of TALLY_GROUP_DTYPE."""
+        out = np.zeros(n, dtype=TALLY_GROUP_DTYPE)
+        _check(self._lib.seeqdevScanCopyTallyHeldRows(self._h, out.ctypes.data if n else None, first, n))
+        return out
+
+    def tally_held_rows_device_ptr(self):
+        """Device address of the last held tally's row table (seeqdev_tally_group_t; valid until this Scanner's next held tally)."""
+        return self._lib.seeqdevScanTallyHeldRowsDevice(self._h)
+
+    def held_matrix(self, nrows, ncols, out=None):
+        """The dense count matrix of the last tally_held(member_columns >= 1), scattered on the device: cell [r - 1, c - 1] is the count
+        of the key with row r and column part c (demux keys and library ids are 1-based); keys outside 1 .. nrows x 1 .. ncols are
+        counted, not stored.  out: a contiguous int64 CUDA tensor of shape [nrows, ncols] to fill (every cell is written), None: a new
+        one on the current CUDA device.  -> (the tensor, dict: ninside, noutside, inside_reads, outside_reads).  SeeqDeviceError
+        (EINVAL) when this Scanner's tally table is no held tally's (a plain or library tally since), E2BIG beyond 2^28 cells."""
+        import torch
+        nrows, ncols = int(nrows), int(ncols)
+        if not (0 <= nrows <= 0xFFFFFFFF and 0 <= ncols <= 0xFFFFFFFF):
+            raise ValueError("held_matrix: %d x %d is no matrix shape" % (nrows, ncols))
+        if out is None:
+            # (a shape the C entry refuses -- no cell, or more than 2^28 -- is refused there, before d_out is touched: nothing is allocated for it)
+            fits = 0 < nrows * ncols <= _capi.SEEQDEV_TALLY_DENSE_MAX
+            out = torch.empty((nrows, ncols) if fits else (0, 0), dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()))
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (nrows, ncols)):
+            raise ValueError("held_matrix: out must be a contiguous int64 CUDA tensor of shape (%d, %d)" % (nrows, ncols))
+        cnt = _capi.seeqdev_tally_dense_counts_t()
+        _check(self._lib.seeqdevScanTallyHeldDense(self._h, C.c_void_p(out.data_ptr() if out.numel() else 16), nrows, ncols, C.byref(cnt)))
+        return out, {name: int(getattr(cnt, name)) for name, _ in _capi.seeqdev_tally_dense_counts_t._fields_}
+
+    def last_tally_held_ms(self):
+        """Device time of the last held tally or held_matrix, whichever came last (profiling on), 0 when not measured."""
+        ms = C.c_float(0)
+        _check(self._lib.seeqdevScanLastTallyHeldMs(self._h, C.byref(ms)))
+        return float(ms.value)
+
     # ---- the base-quality gate in front of the tallies (include/seeq_amd.h: seeqdevScanQualityGate) ----
     def quality_gate(self, t=None, source="inserts", min_qual=20, base=33, max_low=0, reach=1024, copy=True):
         """Keep the spans of `source` ("inserts", "hits" or "anchored", t as in tally()) whose FASTQ quality bytes are good enough: a span passes when
@@ -945,6 +998,15 @@ def hold_split(keys, widths):
         out.append(rest & np.uint64((1 << w) - 1))
         rest = rest >> np.uint64(w)
     return tuple(reversed(out))
+
+
+def held_cell(key, shift, nrows, ncols):
+    """Where Scanner.held_matrix puts the count of a held word (seeqdevTallyHeldCell, on the host): with r = key >> shift and
+    c = key & ((1 << shift) - 1), the flat index (r - 1) * ncols + (c - 1) when 1 <= r <= nrows and 1 <= c <= ncols, else None."""
+    cell = C.c_uint64(0)
+    rc = _capi.lib().seeqdevTallyHeldCell(int(key), int(shift), int(nrows), int(ncols), C.byref(cell))
+    _check(min(rc, 0))
+    return int(cell.value) if rc == 1 else None
 
 
 # One row of seeqdevScanTallyCollapse's group rows (seeq_amd.h: seeqdev_tally_collapse_t, 16 bytes).
